@@ -24,9 +24,12 @@ core/hbv_stack.h:278-361) on 512K cells per GPU, so that --gpus 8 is the
 
 Extra fields: roofline (dominant kernel = ptgsk_run_kernel, HBM-bound
 accounting per SURVEY.md §8d, kernel time from HIP events on the region's
-stream) and cpu_baseline (the CPU oracle built with the host libm, run with the
-reference's scheduler -- use_ncore std::async workers pulling one cell per
-mutex-protected pos++, region_model.h:991-1021 -- on a bounded sample).
+stream) and, with --full only, cpu_baseline (the CPU oracle built with the host
+libm, run with the reference's scheduler -- use_ncore std::async workers pulling
+one cell per mutex-protected pos++, region_model.h:991-1021 -- on a bounded
+sample). A plain run does nothing beyond its timed steps: it sets up, warms up,
+times --steps steps, saves the last step's outputs if --dump-outputs DIR is
+given, and prints the line.
 """
 from __future__ import annotations
 
@@ -107,9 +110,18 @@ def parse(argv=None):
                          "chunk before its run). Default: -1 for a region too small to fill the GPU (<= 131,072 "
                          "cells per GPU), else 0")
     ap.add_argument("--chunk", type=int, default=CHUNK)
-    ap.add_argument("--cpu-cells", type=int, default=4000, help="cpu_baseline sample cells (x 8760 steps)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="0: min(16, os cpu share)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the cpu_baseline (the "
+                         "CPU oracle over a sample of the region, a run of its own). A plain run sets up, warms up, "
+                         "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 saves what the last timed step computed as DIR/<name>.npy (float64): avg_discharge and "
+                         "charge_m3s [chunk][sample] and the final state [sample][fields] of a fixed, seeded sample of "
+                         "this rank's cells (sample_cell_index), the step's catchment discharge sums [C][chunk], and "
+                         "the last chunk of the routed river series [3][R][chunk]; at most 64 MB in all")
+    ap.add_argument("--cpu-cells", type=int, default=4000, help="--full: cpu_baseline sample cells (x 8760 steps)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: 0: min(16, os cpu share)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline")
     ap.add_argument("--idw", action="store_true",
                     help="configs[2]: forcing interpolated each chunk by IDW from 500 stations (run_interpolation) "
                          "instead of the per-cell generator")
@@ -727,6 +739,41 @@ def dist_check(a, world, rank, pg):
         pg.destroy_process_group()
 
 
+DUMP_SEED = 20251015             # the sample of cells --dump-outputs saves: fixed, so two builds save the same cells
+DUMP_SAMPLE_CELLS = 4096
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, r, L, chunk, k_steps, sums, router):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 .npy files under `path`.
+    `r` is the region that ran the last chunk (its window is still that chunk). The per-cell arrays -- the collected
+    avg_discharge and charge_m3s rows of the chunk and the state the chunk left -- are saved for a seeded sample of
+    this rank's cells (all of them if the region is smaller), sized so that everything stays below DUMP_MAX_BYTES."""
+    from shyft_amd.region import STACK_NSTATE
+    os.makedirs(path, exist_ok=True)
+    step0 = (k_steps - 1) * chunk
+    out = {}
+    if sums is not None:
+        out["catchment_sums"] = sums.sums[:, step0:step0 + chunk].cpu().numpy()
+    if router is not None and router.out is not None:
+        out["routed"] = np.stack(router.out)[:, :, step0:step0 + chunk]
+    # whole catchments / rivers from the top if a region has so many that they alone would pass a quarter of the limit
+    for name, v in out.items():
+        rows = max(1, (DUMP_MAX_BYTES // 4) // (v.size // v.shape[-2] * 8))
+        out[name] = v[..., :rows, :]
+    left = DUMP_MAX_BYTES - sum(v.size * 8 for v in out.values())
+    per_cell = (2 * chunk + STACK_NSTATE[r.stack] + 1) * 8
+    k = max(1, min(L.n, DUMP_SAMPLE_CELLS, left // per_cell))
+    cells = (np.arange(L.n) if k == L.n else
+             np.sort(np.random.default_rng(DUMP_SEED).choice(L.n, size=k, replace=False)))
+    out["sample_cell_index"] = (L.off + cells).astype(np.float64)
+    out["avg_discharge"] = r.sample_cells(0, cells, step0, chunk)
+    out["charge_m3s"] = r.sample_cells(1, cells, step0, chunk)
+    out["state"] = r.get_state()[cells]
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def supervisor_info():
     """The `supervisor` field of a rank's line: which attempt produced it and why the one before ended."""
     if os.environ.get("SHYFT_SUPERVISED") != "1":
@@ -995,7 +1042,11 @@ def main():
             np.save(a.dump_sums, tot.cpu().numpy())
     if supervisor_info() is not None:
         out["supervisor"] = supervisor_info()
-    if rank == 0 and world == 1 and not devices and not a.no_cpu_baseline:
+    if a.dump_outputs and rank == 0:
+        # the region that ran the last chunk (the pipelined path alternates between two)
+        dump_outputs(a.dump_outputs, r_alt if r_alt is not None and a.steps % 2 == 0 else r, L, chunk, a.steps, sums,
+                     router)
+    if a.full and rank == 0 and world == 1 and not devices and not a.no_cpu_baseline:
         threads = a.cpu_threads or min(16, len(os.sched_getaffinity(0)))
         out["cpu_baseline"] = (cpu_baseline_idw(a.cpu_cells, threads) if a.idw and not a.btk and a.stack == "pt_gs_k"
                                else cpu_baseline(a.stack, a.cpu_cells, threads))

@@ -55,6 +55,20 @@ def _store(world: int, rank: int, timeout_s: float):
                     wait_for_workers=False)
 
 
+def _leave(store, key: str, world: int, rank: int) -> None:
+    """A final decision ("done" / "fail") has been read: the other ranks say so, and rank 0 -- whose process may host
+    the store -- waits for them (bounded) before it goes on to exit, so that no rank finds the store gone while it
+    still polls for the decision."""
+    from datetime import timedelta
+    try:
+        if rank != 0:
+            store.set(f"{key}/seen/{rank}", "1")
+        elif world > 1:
+            store.wait([f"{key}/seen/{r}" for r in range(1, world)], timedelta(seconds=30))
+    except Exception:  # noqa: BLE001 -- a rank that is gone cannot answer; the decision stands
+        pass
+
+
 class _Child:
     """One attempt's worker process: stdout forwarded line by line (rank 0's JSON line noticed), stderr forwarded and
     scanned for progress markers."""
@@ -151,6 +165,8 @@ def supervise(argv, attempts=ATTEMPTS) -> int:
                         child.kill()
                         break
             time.sleep(0.2)
+        if not decision.startswith("retry"):
+            _leave(store, key, world, rank)
         if decision == "done":
             # the line is out; let the child finish its teardown, but not forever
             t_end = time.monotonic() + stall_s

@@ -184,6 +184,34 @@ def test_overlapped_forcing_generation_same_results(tmp_path, cus):
 
 
 @pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run times its steps and prints the line without the cpu_baseline; --full adds it and changes nothing
+    else. --dump-outputs saves the last step's outputs as float64 (per-cell arrays for a seeded sample of 4096 of the
+    region's 5000 cells), and two runs of the same arguments save identical files. --steps sets the timed steps and
+    ms_per_step is one of them: the value is the cell-steps over steps x ms_per_step."""
+    common = ["--gpus", "1", "--stack", "pt_ss_k", "--total-cells", "5000", "--catchments", "20", "--chunk", "48",
+              "--steps", "4", "--warmup", "1"]
+    p1, o1 = _bench(common + ["--dump-outputs", str(tmp_path / "a")])
+    assert p1.returncode == 0, p1.stderr[-2000:]
+    p2, o2 = _bench(common + ["--dump-outputs", str(tmp_path / "b"), "--full", "--cpu-cells", "64"])
+    assert p2.returncode == 0, p2.stderr[-2000:]
+    assert "cpu_baseline" not in o1 and o2["cpu_baseline"]["value"] > 0
+    assert o1["steps"] == 4 and len(o1["chunk_kernel_ms"]) == 4 and o1["ms_per_step"] > 0
+    assert o1["value"] == pytest.approx(5000 * 48 * 4 / (o1["ms_per_step"] * 4e-3))
+    shapes = {"sample_cell_index": (4096,), "avg_discharge": (48, 4096), "charge_m3s": (48, 4096), "state": (4096, 8),
+              "catchment_sums": (20, 48), "routed": (3, 20, 48)}
+    assert sorted(f.name for f in (tmp_path / "a").iterdir()) == sorted(k + ".npy" for k in shapes)
+    for name, shape in shapes.items():
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float64 and x.shape == shape and np.isfinite(x).all(), name
+        assert np.array_equal(x, y), name
+    ix = np.load(tmp_path / "a" / "sample_cell_index.npy")
+    assert np.all(np.diff(ix) > 0) and ix[0] >= 0 and ix[-1] < 5000 and np.array_equal(ix, np.floor(ix))
+    assert np.load(tmp_path / "a" / "avg_discharge.npy").sum() > 0
+    assert np.load(tmp_path / "a" / "catchment_sums.npy").sum() > 0
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("stack", ["pt_gs_k", "pt_ss_k"])
 def test_engine_shards_one_process_match_unsharded(stack, tmp_path):
     """bench's single-process engine path with two shards on device 0: the per-chunk catchment discharge sums and

@@ -28,8 +28,9 @@ ARGS[btk]="--btk --steps 20 --warmup 1 --no-cpu-baseline";                   KER
 python3 -c "from shyft_amd import _native; print(_native.lib_sha())" > $OUT/lib_sha.txt || exit 1
 for name in $LINES; do
     [ -n "${ARGS[$name]}" ] || { echo "unknown line $name"; exit 1; }
-    echo "line $name: python3 bench.py ${ARGS[$name]}"
-    timeout -k 10 ${LIMIT[$name]} python3 bench.py ${ARGS[$name]} > $OUT/$name.json 2> $OUT/$name.err \
+    # --full: the recorded line carries the cpu_baseline too (the profile passes below run the plain command)
+    echo "line $name: python3 bench.py ${ARGS[$name]} --full"
+    timeout -k 10 ${LIMIT[$name]} python3 bench.py ${ARGS[$name]} --full > $OUT/$name.json 2> $OUT/$name.err \
         || { echo "LINE $name FAILED"; tail -20 $OUT/$name.err; exit 1; }
     python3 -c "import json,sys; d=json.load(open('$OUT/$name.json')); print('  value %.4g cell-steps/s, %.2f ms/step, kernel %.2f ms' % (d['value'], d['ms_per_step'], d['kernel_ms_per_step']))"
 done
