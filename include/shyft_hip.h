@@ -347,6 +347,37 @@ double shyft_hip_ensemble_last_ms(const shyft_hip_region* h);
  * tests to show device math == host math bit for bit. */
 int shyft_hip_math_selftest(int fn, const double* x, const double* y, size_t n, double* out);
 
+/* Diagnostic: the device-only restatements of the hot paths (device/fastmath.h, special.h, gamma_lean.h,
+ * gs_brent.h, ptssk_dev.h) on n host rows, one row per job, evaluated by test kernels that live in the kernel file
+ * whose run kernel uses them (pt_gs_k: elementary functions as out-of-line detmath calls; pt_ss_k: the SGPR-table
+ * calls). in[n_in_cols][n] and out[n_out_cols][n] are host arrays, column-major. Returns non-zero on an unknown
+ * fn, a column count that is not the function's, a null array or a HIP error.
+ *   fn                                in columns                  out columns
+ *   EXPLOG_INLINE  (pt_gs_k)          x                           exp_fast(x), log_fast(x)
+ *   EXPLOG_CALLS   (pt_gs_k)          x, y                        dexp(x), dlog(x), dexp2(x, y).a, .b
+ *   EXPLOG_TABLE   (pt_ss_k)          x, y                        the same functions as built there
+ *   POWERS         (pt_gs_k)          x, y                        dpowr(x, y), dpow4(x), dpow8(x), dpow(x, y)
+ *   GAMMA_LEAN     (pt_gs_k)          a, x                        p, p1, prefix of gs_gamma_pq_cs; ok (0 / 1) of
+ *                                                                 gsb_gamma_pq at gamma_snow's policy eps
+ *   BRENT          (pt_gs_k)          z1, a1, b1, a2, b2, mode    gs_corr_lwc, gs_corr_lwc_lean
+ *   BRENT_SPEC4 / BRENT_SPEC2         the same                    gs_corr_lwc_spec on 4 / 2 lanes per job, then
+ *                                                                 gs_corr_lwc_memo, as the small-region run kernel
+ *   SKAUGEN        (pt_ss_k)          u, n, nu_a, alpha           ss_sca_rel_red, its error code
+ *   SKAUGEN_GROUP2 / SKAUGEN_GROUP4   the same                    ss_sca_rel_red_group on 2 / 4 lanes per job
+ * Brent mode 0: Q1 is not supplied (q1 = NaN, the job evaluates it); mode 1: q1 = calc_q(a1, b1, z1). */
+#define SHYFT_HIP_DST_EXPLOG_INLINE 0
+#define SHYFT_HIP_DST_EXPLOG_CALLS 1
+#define SHYFT_HIP_DST_EXPLOG_TABLE 2
+#define SHYFT_HIP_DST_POWERS 3
+#define SHYFT_HIP_DST_GAMMA_LEAN 4
+#define SHYFT_HIP_DST_BRENT 5
+#define SHYFT_HIP_DST_BRENT_SPEC4 6
+#define SHYFT_HIP_DST_BRENT_SPEC2 7
+#define SHYFT_HIP_DST_SKAUGEN 8
+#define SHYFT_HIP_DST_SKAUGEN_GROUP2 9
+#define SHYFT_HIP_DST_SKAUGEN_GROUP4 10
+int shyft_hip_device_selftest(int fn, const double* in, size_t n_in_cols, size_t n, double* out, size_t n_out_cols);
+
 #ifdef __cplusplus
 }
 #endif

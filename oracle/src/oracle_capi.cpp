@@ -291,6 +291,69 @@ extern "C" void oracle_gamma_pq_policy(double a, double x, double* p, double* p1
     *prefix = r.prefix;
 }
 
+// How many times detmath::gamma_pq's series (x < a + 1) or continued fraction rescales by 2^-200 for (a, x, eps):
+// the loops of detmath::gamma_series_sums / gamma_cf_terms (their term-by-term form) restated with a counter beside
+// the rescale. 0 for the special cases (NaN, x <= 0, x = inf), which run neither. The lean device evaluation
+// (device/gamma_lean.h) has no rescale and must hand such an (a, x) to the general one.
+extern "C" int oracle_gamma_pq_rescaled(double a, double x, double eps) {
+    const int kind = detmath::gamma_pq_kind(a, x);
+    int count = 0;
+    if (kind == detmath::GPQ_SERIES) {
+        double ap = a, E = 1.0, B = 0.0, xn = 1.0;
+        for (int n = 1; n <= 2000; ++n) {
+            ap = ap + 1.0;
+            xn = xn * x;
+            E = E * ap;
+            B = std::fma(B, ap, xn);
+            if (xn < eps * (B + E)) break;
+            if (E > detmath::GPQ_SCALE_HI) {
+                E = E * detmath::GPQ_SCALE;
+                B = B * detmath::GPQ_SCALE;
+                xn = xn * detmath::GPQ_SCALE;
+                ++count;
+            }
+        }
+    } else if (kind == detmath::GPQ_CF) {
+        double b = x + 1.0 - a, Pm = 1.0, Qm = 0.0, P = b, Qd = 1.0, di = 0.0;
+        for (int i = 1; i <= 2000; ++i) {
+            di = di + 1.0;
+            const double an = -di * (di - a);
+            b = b + 2.0;
+            const double Pn = std::fma(b, P, an * Pm);
+            const double Qn = std::fma(b, Qd, an * Qm);
+            const double cross = Pn * Qd;
+            const double diff = cross - P * Qn;
+            Pm = P; Qm = Qd;
+            P = Pn; Qd = Qn;
+            if (std::fabs(diff) <= eps * std::fabs(cross)) break;
+            if (std::fabs(P) > detmath::GPQ_SCALE_HI) {
+                P = P * detmath::GPQ_SCALE; Qd = Qd * detmath::GPQ_SCALE; Pm = Pm * detmath::GPQ_SCALE; Qm = Qm * detmath::GPQ_SCALE;
+                ++count;
+            }
+        }
+    }
+    return count;
+}
+
+// the structured powers of this build (mathlib.hpp)
+extern "C" double oracle_powr(double x, double y) { return OPOWR(x, y); }
+extern "C" double oracle_pow4(double x) { return OPOW4(x); }
+extern "C" double oracle_pow8(double x) { return OPOW8(x); }
+
+// oracle_skaugen_sca_rel_red with what it raises reported instead of thrown: 0 and *out = the value; 1 the pdf's
+// pole at x = 0 of a shape < 1 (boost's overflow_error); 2 bisect's evaluation_error (no change of sign, or
+// arguments in the wrong order). *out is left alone on 1 and 2.
+extern "C" int oracle_skaugen_sca_rel_red_checked(uint64_t u, uint64_t n, double nu_a, double alpha, double* out) {
+    try {
+        *out = skaugen::statistics::sca_rel_red(u, n, 0.0, nu_a, alpha);
+    } catch (const std::overflow_error&) {
+        return 1;
+    } catch (const std::runtime_error&) {
+        return 2;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------- hbv_stack
 // Snow distribution row per parameter set: n_bins, s[8], intervals[8] (17 doubles).
 namespace {

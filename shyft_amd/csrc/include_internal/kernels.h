@@ -38,6 +38,13 @@ struct ptgsk_kargs {
 
 hipError_t launch_ptgsk_run(const ptgsk_kargs& a, hipStream_t stream);
 
+// Diagnostic (shyft_hip_device_selftest, include/shyft_hip.h): the device functions of one kernel file on chosen
+// inputs, run from that file so that the out-of-line functions are the instances its run kernel calls.
+// in [n_in_cols][n] and out [n_out_cols][n] are device arrays; fn is a SHYFT_HIP_DST_* code of that file.
+// hipErrorInvalidValue for a code the file does not serve.
+hipError_t launch_ptgsk_selftest(int fn, const double* in, size_t n, double* out, hipStream_t stream);
+hipError_t launch_ptssk_selftest(int fn, const double* in, size_t n, double* out, hipStream_t stream);
+
 struct hbv_kargs {
     int n_cells, step0, n_steps, win0, win_len, collect;
     double step_in_days;     // to_seconds(dt)/86400

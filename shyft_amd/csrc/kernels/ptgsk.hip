@@ -23,6 +23,7 @@
 #include "../device/stream.h"
 #include "../device/wave_place.h"
 #include "../include_internal/kernels.h"
+#include "../../../include/shyft_hip.h"
 
 using namespace shyft_dev;
 
@@ -401,6 +402,121 @@ __global__ __launch_bounds__(256, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_callee_bu
     a.resp[c] = q + qa + sca + sto + s.lwc;
 }
 
+// ---- diagnostic kernels (shyft_hip_device_selftest): this file's device functions on chosen inputs, one thread per
+// row, in [col][n] -> out [col][n]. They live here so that the out-of-line functions they call (dexp, dlog, dexp2,
+// dlgamma, gs_gamma_pq_general, gs_corr_lwc_lean, gs_corr_lwc_spec, gs_corr_lwc_memo ...) are the instances the run
+// kernels call, and they carry the occupancy bounds of a kernel that already calls those functions (the callee
+// budget kernel's, or the speculative instance's), so the functions are compiled as before.
+constexpr int ST_BLOCK = 256;
+
+__global__ __launch_bounds__(ST_BLOCK, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_st_explog_inline_kernel(
+    const double* __restrict__ in, size_t n, double* __restrict__ out) {
+    const size_t i = blockIdx.x * (size_t)ST_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const kmath<true> km;  // the step loop's inline exp / log (device/pt_dev.h)
+    const double x = in[i];
+    out[i] = km.exp(x);
+    out[n + i] = km.log(x);
+}
+
+__global__ __launch_bounds__(ST_BLOCK, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_st_explog_calls_kernel(
+    const double* __restrict__ in, size_t n, double* __restrict__ out) {
+    const size_t i = blockIdx.x * (size_t)ST_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double x = in[i], y = in[n + i];
+    out[i] = dexp(x);
+    out[n + i] = dlog(x);
+    const dexp_pair e = dexp2(x, y);
+    out[2 * n + i] = e.a;
+    out[3 * n + i] = e.b;
+}
+
+__global__ __launch_bounds__(ST_BLOCK, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_st_powers_kernel(
+    const double* __restrict__ in, size_t n, double* __restrict__ out) {
+    const size_t i = blockIdx.x * (size_t)ST_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double x = in[i], y = in[n + i];
+    out[i] = dpowr(x, y);
+    out[n + i] = dpow4(x);
+    out[2 * n + i] = dpow8(x);
+    out[3 * n + i] = dpow(x, y);
+}
+
+// the lean incomplete gamma's own verdict (ok) beside calc_snow_state's evaluation, which redoes a lane that is not ok
+__global__ __launch_bounds__(ST_BLOCK, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_st_gamma_kernel(
+    const double* __restrict__ in, size_t n, double* __restrict__ out) {
+    const size_t i = blockIdx.x * (size_t)ST_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double a = in[i], x = in[n + i];
+    const double lga = dlgamma(a);
+    bool ok;
+    (void)gsb_gamma_pq(a, x, lga, detmath::gamma_snow_policy_eps(a), a + 1.0, gsb_load(), ok);
+    const gamma_p_result r = gs_gamma_pq_cs(a, x, lga);
+    out[i] = r.p;
+    out[n + i] = r.p1;
+    out[2 * n + i] = r.prefix;
+    out[3 * n + i] = ok ? 1.0 : 0.0;
+}
+
+// Q1 as the job's lane supplies it: NaN (mode 0), or calc_q at the opening point (mode 1)
+__device__ __forceinline__ double st_brent_q1(double mode, double z1, double a1, double b1) {
+    return mode != 0.0 ? gs_calc_q(a1, b1, z1, dlgamma(a1)) : __builtin_nan("");
+}
+
+__global__ __launch_bounds__(ST_BLOCK, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_st_brent_kernel(
+    const double* __restrict__ in, size_t n, double* __restrict__ out) {
+    const size_t i = blockIdx.x * (size_t)ST_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double z1 = in[i], a1 = in[n + i], b1 = in[2 * n + i], a2 = in[3 * n + i], b2 = in[4 * n + i];
+    const double q1 = st_brent_q1(in[5 * n + i], z1, a1, b1);
+    const double lga2 = dlgamma(a2);
+#ifdef SHYFT_PROF
+    int nf_evals = 0;
+    out[i] = gs_corr_lwc(z1, a1, b1, a2, b2, q1, lga2, nf_evals);
+#else
+    out[i] = gs_corr_lwc(z1, a1, b1, a2, b2, q1, lga2);
+#endif
+    out[n + i] = GS_BRENT_JOB(z1, a1, b1, a2, b2, q1, lga2);
+}
+
+// the speculative opening as the small-region instance of ptgsk_run_kernel runs it: one wavefront per workgroup,
+// its 64 / L jobs queued in LDS, L point lanes per job, a barrier, then the memo solve by lane t for job t
+template <int L>
+__global__ __launch_bounds__(64, 2) void ptgsk_st_brent_spec_kernel(const double* __restrict__ in, size_t n,
+                                                                    double* __restrict__ out) {
+    static_assert(L == 4 || L == 2, "4 or 2 point lanes per job");
+    constexpr int JOBS = 64 / L;
+    __shared__ double jz1[JOBS], ja1[JOBS], jb1[JOBS], ja2[JOBS], jb2[JOBS], jq1[JOBS], jlg2[JOBS];
+    __shared__ double jsz[64], jsf[64];
+    const int t = threadIdx.x;
+    const size_t j0 = blockIdx.x * (size_t)JOBS;
+    const int nj = n - j0 < (size_t)JOBS ? (int)(n - j0) : JOBS;  // the launch has no workgroup beyond the jobs
+    if (t < nj) {
+        const size_t i = j0 + t;
+        jz1[t] = in[i]; ja1[t] = in[n + i]; jb1[t] = in[2 * n + i]; ja2[t] = in[3 * n + i]; jb2[t] = in[4 * n + i];
+        jq1[t] = st_brent_q1(in[5 * n + i], jz1[t], ja1[t], jb1[t]);
+        jlg2[t] = dlgamma(ja2[t]);
+    }
+    __syncthreads();
+    const int jj = L == 4 ? t >> 2 : t >> 1;
+    if (t < 64 && jj < nj) {
+        const gsb_zf r = gs_corr_lwc_spec(jz1[jj], ja1[jj], jb1[jj], ja2[jj], jb2[jj], jq1[jj], jlg2[jj], t & (L - 1));
+        jsz[t] = r.z;
+        jsf[t] = r.f;
+    }
+    __syncthreads();
+    if (t < nj) {
+        gsb_memo mm;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {  // with 2 points, entries 2 and 3 repeat entry 0
+            const int e = L * t + (k < L ? k : 0);
+            mm.z[k] = jsz[e];
+            mm.f[k] = jsf[e];
+        }
+        out[j0 + t] = gs_corr_lwc_memo(jz1[t], ja1[t], jb1[t], ja2[t], jb2[t], jq1[t], jlg2[t], mm);
+    }
+}
+
 }  // namespace
 
 
@@ -433,6 +549,26 @@ hipError_t launch_ptgsk_run(const ptgsk_kargs& a, hipStream_t stream) {
         // its memo registers spill in every phase of the 128-VGPR step loop, so it stays a small-region feature)
         if (a.uniform_params) hipLaunchKernelGGL((ptgsk_run_kernel<true, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
         else hipLaunchKernelGGL((ptgsk_run_kernel<true, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_ptgsk_selftest(int fn, const double* in, size_t n, double* out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + ST_BLOCK - 1) / ST_BLOCK)), block(ST_BLOCK);
+    switch (fn) {
+        case SHYFT_HIP_DST_EXPLOG_INLINE: hipLaunchKernelGGL(ptgsk_st_explog_inline_kernel, grid, block, 0, stream, in, n, out); break;
+        case SHYFT_HIP_DST_EXPLOG_CALLS: hipLaunchKernelGGL(ptgsk_st_explog_calls_kernel, grid, block, 0, stream, in, n, out); break;
+        case SHYFT_HIP_DST_POWERS: hipLaunchKernelGGL(ptgsk_st_powers_kernel, grid, block, 0, stream, in, n, out); break;
+        case SHYFT_HIP_DST_GAMMA_LEAN: hipLaunchKernelGGL(ptgsk_st_gamma_kernel, grid, block, 0, stream, in, n, out); break;
+        case SHYFT_HIP_DST_BRENT: hipLaunchKernelGGL(ptgsk_st_brent_kernel, grid, block, 0, stream, in, n, out); break;
+        case SHYFT_HIP_DST_BRENT_SPEC4:  // 16 jobs per one-wavefront workgroup
+            hipLaunchKernelGGL(ptgsk_st_brent_spec_kernel<4>, dim3((unsigned)((n + 15) / 16)), dim3(64), 0, stream, in, n, out);
+            break;
+        case SHYFT_HIP_DST_BRENT_SPEC2:  // 32 jobs
+            hipLaunchKernelGGL(ptgsk_st_brent_spec_kernel<2>, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, stream, in, n, out);
+            break;
+        default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

@@ -43,6 +43,7 @@ extern "C" int shyft_ptssk_prof_read(unsigned long long* out) {
 #include "../device/stream.h"
 #include "../device/wave_place.h"
 #include "../include_internal/kernels.h"
+#include "../../../include/shyft_hip.h"
 
 using namespace shyft_dev;
 
@@ -368,6 +369,52 @@ __global__ __launch_bounds__(256, 8) void ptssk_callee_budget_kernel(const ptssk
 }
 #endif
 
+// ---- diagnostic kernels (shyft_hip_device_selftest): this file's out-of-line device functions on chosen inputs,
+// in [col][n] -> out [col][n]: the instances the run kernel calls, compiled for the callee budget kernel's occupancy
+constexpr int ST_WAVES = 8;
+
+// dexp / dlog / dexp2 with their constants from the SGPR table (SHYFT_TABLE_CALLS 1)
+__global__ __launch_bounds__(BLOCK, ST_WAVES) void ptssk_st_explog_kernel(const double* __restrict__ in, size_t n,
+                                                                          double* __restrict__ out) {
+    const size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double x = in[i], y = in[n + i];
+    out[i] = dexp(x);
+    out[n + i] = dlog(x);
+    const dexp_pair e = dexp2(x, y);
+    out[2 * n + i] = e.a;
+    out[3 * n + i] = e.b;
+}
+
+// one lane per job
+__global__ __launch_bounds__(BLOCK, ST_WAVES) void ptssk_st_job_kernel(const double* __restrict__ in, size_t n,
+                                                                       double* __restrict__ out) {
+    const size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x;
+    if (i >= n) return;
+    int32_t e = 0;
+    out[i] = ss_sca_rel_red((uint64_t)in[i], (uint64_t)in[n + i], in[2 * n + i], in[3 * n + i], e);
+    out[n + i] = (double)e;
+}
+
+// L consecutive lanes per job, as the run kernel's solving wavefronts: job j = t / L, lane k = t & (L - 1), the
+// result taken from lane 0. A group's lanes share j, so a group leaves or stays as a whole (grp_get reads every lane
+// of the group), and the workgroup size is a multiple of L.
+template <int L>
+__global__ __launch_bounds__(BLOCK, ST_WAVES) void ptssk_st_group_kernel(const double* __restrict__ in, size_t n,
+                                                                         double* __restrict__ out) {
+    static_assert(L == 2 || L == 4, "groups of 2 or 4 lanes");
+    const size_t t = blockIdx.x * (size_t)BLOCK + threadIdx.x;
+    const size_t j = t / L;
+    const int k = (int)(t & (L - 1));
+    if (j >= n) return;
+    int32_t e = 0;
+    const double r = ss_sca_rel_red_group((uint64_t)in[j], (uint64_t)in[n + j], in[2 * n + j], in[3 * n + j], L, k, e);
+    if (k == 0) {
+        out[j] = r;
+        out[n + j] = (double)e;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_ptssk_run(const ptssk_kargs& a, hipStream_t stream) {
@@ -378,5 +425,18 @@ hipError_t launch_ptssk_run(const ptssk_kargs& a, hipStream_t stream) {
 #endif
     if (a.uniform_params) hipLaunchKernelGGL((ptssk_run_kernel<true, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
     else hipLaunchKernelGGL((ptssk_run_kernel<true, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ptssk_selftest(int fn, const double* in, size_t n, double* out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    auto grid = [&](size_t threads) { return dim3((unsigned)((threads + BLOCK - 1) / BLOCK)); };
+    switch (fn) {
+        case SHYFT_HIP_DST_EXPLOG_TABLE: hipLaunchKernelGGL(ptssk_st_explog_kernel, grid(n), dim3(BLOCK), 0, stream, in, n, out); break;
+        case SHYFT_HIP_DST_SKAUGEN: hipLaunchKernelGGL(ptssk_st_job_kernel, grid(n), dim3(BLOCK), 0, stream, in, n, out); break;
+        case SHYFT_HIP_DST_SKAUGEN_GROUP2: hipLaunchKernelGGL(ptssk_st_group_kernel<2>, grid(2 * n), dim3(BLOCK), 0, stream, in, n, out); break;
+        case SHYFT_HIP_DST_SKAUGEN_GROUP4: hipLaunchKernelGGL(ptssk_st_group_kernel<4>, grid(4 * n), dim3(BLOCK), 0, stream, in, n, out); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }

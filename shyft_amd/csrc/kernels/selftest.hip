@@ -6,6 +6,7 @@
 
 #include "../../../include/shyft_hip.h"
 #include "../device/special.h"
+#include "../include_internal/kernels.h"
 
 namespace {
 
@@ -43,6 +44,35 @@ extern "C" int shyft_hip_math_selftest(int fn, const double* x, const double* y,
 done:
     if (dx) (void)hipFree(dx);
     if (dy) (void)hipFree(dy);
+    if (dout) (void)hipFree(dout);
+    return rc;
+}
+
+// The device-only restatements of the hot paths, by the test kernels of the kernel file that uses them
+// (launch_ptgsk_selftest / launch_ptssk_selftest).
+extern "C" int shyft_hip_device_selftest(int fn, const double* in, size_t n_in_cols, size_t n, double* out,
+                                         size_t n_out_cols) {
+    // in / out columns of each function code, and the kernel file that serves it
+    static const struct { size_t n_in, n_out; bool ptssk; } spec[] = {
+        {1, 2, false}, {2, 4, false}, {2, 4, true}, {2, 4, false}, {2, 4, false}, {6, 2, false},
+        {6, 1, false}, {6, 1, false}, {4, 2, true}, {4, 2, true}, {4, 2, true}};
+    if (fn < 0 || fn >= (int)(sizeof spec / sizeof spec[0]) || !in || !out) return 1;
+    if (n_in_cols != spec[fn].n_in || n_out_cols != spec[fn].n_out) return 1;
+    if (n == 0) return 0;
+    double *din = nullptr, *dout = nullptr;
+    int rc = 1;
+    if (hipMalloc(&din, n_in_cols * n * sizeof(double)) != hipSuccess) goto done;
+    if (hipMalloc(&dout, n_out_cols * n * sizeof(double)) != hipSuccess) goto done;
+    if (hipMemcpy(din, in, n_in_cols * n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) goto done;
+    if (hipMemset(dout, 0xff, n_out_cols * n * sizeof(double)) != hipSuccess) goto done;  // unwritten = NaN
+    if ((spec[fn].ptssk ? launch_ptssk_selftest(fn, din, n, dout, 0) : launch_ptgsk_selftest(fn, din, n, dout, 0)) !=
+        hipSuccess)
+        goto done;
+    if (hipDeviceSynchronize() != hipSuccess) goto done;
+    if (hipMemcpy(out, dout, n_out_cols * n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) goto done;
+    rc = 0;
+done:
+    if (din) (void)hipFree(din);
     if (dout) (void)hipFree(dout);
     return rc;
 }
