@@ -65,6 +65,13 @@ constexpr int BLOCK = 256;
 #define SHYFT_LB_WAVES 4
 #endif
 
+// the lean instances (LEAN below) take the discharge-only launches (0: every launch takes the general instance, for
+// A/B builds). r06, 1M cells, 20 x 438 steps: 9.81-9.84e9 -> 9.92-9.94e9 cell-steps/s, with machine LICM off for this
+// file (Makefile) 10.17-10.25e9, bit-exact (profiles/r06/ptgsk_lean_instance_ab.txt)
+#ifndef SHYFT_PTGSK_LEAN
+#define SHYFT_PTGSK_LEAN 1
+#endif
+
 // issue priority (s_setprio) of the Brent-solving wavefront: 138.2 -> 134.5 ms per chunk (year mean, 1M cells)
 constexpr int BRENT_PRIO = 3;
 
@@ -79,7 +86,11 @@ constexpr int BRENT_PRIO = 3;
 // the GPU; a region too small to give every SIMD 4 waves (<= 2 workgroups per CU, e.g. a strong-scaled shard of
 // 131K cells) gets the 2-wave instance instead (256 VGPRs, no spills): it cannot be 4-deep anyway.
 // B: cells (lanes) per workgroup. SPEC: the speculative Brent opening (device/gs_brent.h), for small regions.
-template <bool COMPACT, bool UNIFORM, bool ENS = false, int WAVES = SHYFT_LB_WAVES, int B = BLOCK, bool SPEC = false>
+// LEAN: the instance for the common launch (discharge collector only, no state series, no read_delay test knob), as
+// in kernels/hbv.hip: it has no code for response series 2-7, the state series or the knob and holds no pointers for
+// them, which the general instance keeps in SGPRs (spilled to VGPR lanes) across the whole step loop.
+template <bool COMPACT, bool UNIFORM, bool ENS = false, int WAVES = SHYFT_LB_WAVES, int B = BLOCK, bool SPEC = false,
+          bool LEAN = false>
 __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a) {
     static_assert(COMPACT, "the Brent jobs always go through the workgroup queue");
     const int cell = blockIdx.x * blockDim.x + threadIdx.x;
@@ -167,7 +178,7 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
     const double* __restrict__ f_rad = a.forcing + (size_t)FV_RADIATION * TW * NF;
     double* __restrict__ R = a.resp;
     const size_t RS = TW * N;  // stride between response series
-    double* __restrict__ SS = a.state_series;
+    double* __restrict__ SS = LEAN ? nullptr : a.state_series;
     const size_t SSS = (TW + 1) * N;
     const int wed = (int)Pg[PK_WED];
     const int64_t snow_lo = (int64_t)((int)(Pg[PK_WED] * 24) - (int)(Pg[PK_NWD] * 24)) * 3600000000LL;
@@ -289,7 +300,7 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
                 __syncthreads();
                 // test knob: the other wavefronts read their results late, so a fast first wavefront is already
                 // enqueueing the next step's jobs (jres must not alias the job arrays for this to stay exact)
-                if (a.read_delay > 0 && (threadIdx.x >> 6) != 0)
+                if (!LEAN && a.read_delay > 0 && (threadIdx.x >> 6) != 0)
                     for (int k = 0; k < a.read_delay; ++k) __builtin_amdgcn_s_sleep(127);
                 if (slot >= 0) z = jres[slot];
             }
@@ -333,11 +344,11 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
         // collectors (pt_gs_k_cell_model.h:80-89, 116-124) of response.scale_snow(snow_storage_fraction)
         stream_st<STREAM_NT>(&R[0 * RS + fo], cell_area_m2 * total_discharge * mmh_to_m3s_scale_factor);
         stream_st<STREAM_NT>(&R[1 * RS + fo], charge_m3s);
-        if (a.collect >= 1) {
+        if (!LEAN && a.collect >= 1) {
             R[2 * RS + fo] = gs_sca;
             R[3 * RS + fo] = gs_storage * snow_storage_fraction;
         }
-        if (a.collect >= 2) {
+        if (!LEAN && a.collect >= 2) {
             R[4 * RS + fo] = cell_area_m2 * (gs_outflow * snow_storage_fraction) * mmh_to_m3s_scale_factor;
             R[5 * RS + fo] = gm_melt_m3s;
             R[6 * RS + fo] = ae;
@@ -534,6 +545,8 @@ hipError_t launch_ptgsk_run(const ptgsk_kargs& a, hipStream_t stream) {
     }
     static const char* force = getenv("SHYFT_PTGSK_WAVES");  // measurement knob: "2" / "4" forces an instance
     const bool small = a.instance ? a.instance == 2 : force ? force[0] == '2' : grid <= 2 * n_cu;
+    // the discharge-only launch takes the lean instance; every other combination the general one
+    const bool lean = SHYFT_PTGSK_LEAN && a.collect == 0 && !a.state_series && a.read_delay == 0;
     if (a.n_cells < 0)  // never (n_cells > 0): keeps ptgsk_callee_budget_kernel in the module
         hipLaunchKernelGGL(ptgsk_callee_budget_kernel, dim3(1), dim3(BLOCK), 0, stream, a);
     if (a.fcol) {
@@ -542,8 +555,14 @@ hipError_t launch_ptgsk_run(const ptgsk_kargs& a, hipStream_t stream) {
         // small regions: one-wavefront workgroups (each wavefront solves its own ~7 winter Brent jobs: no workgroup
         // barrier wait) with the speculative Brent opening (4 lanes per job, free in a wavefront that has the lanes)
         const int g64 = (a.n_cells + 63) / 64;
-        if (a.uniform_params) hipLaunchKernelGGL((ptgsk_run_kernel<true, true, false, 2, 64, true>), dim3(g64), dim3(64), 0, stream, a);
+        if (lean) {
+            if (a.uniform_params) hipLaunchKernelGGL((ptgsk_run_kernel<true, true, false, 2, 64, true, true>), dim3(g64), dim3(64), 0, stream, a);
+            else hipLaunchKernelGGL((ptgsk_run_kernel<true, false, false, 2, 64, true, true>), dim3(g64), dim3(64), 0, stream, a);
+        } else if (a.uniform_params) hipLaunchKernelGGL((ptgsk_run_kernel<true, true, false, 2, 64, true>), dim3(g64), dim3(64), 0, stream, a);
         else hipLaunchKernelGGL((ptgsk_run_kernel<true, false, false, 2, 64, true>), dim3(g64), dim3(64), 0, stream, a);
+    } else if (lean) {
+        if (a.uniform_params) hipLaunchKernelGGL((ptgsk_run_kernel<true, true, false, SHYFT_LB_WAVES, BLOCK, false, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((ptgsk_run_kernel<true, false, false, SHYFT_LB_WAVES, BLOCK, false, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
     } else {
         // (the speculative Brent opening in this instance measured 100.5 -> 134.7 ms per 1M-cell chunk, year mean:
         // its memo registers spill in every phase of the 128-VGPR step loop, so it stays a small-region feature)
