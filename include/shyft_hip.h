@@ -207,6 +207,30 @@ int shyft_hip_btk(int device, size_t n_sources, const double* src_xyz, const dou
                   const double* prior_gradient, const double* btk_param, size_t n_dst, const double* dst_xyz,
                   double* out);
 
+/* Stateless ordinary kriging (api/boostpython/api_interpolation.cpp:86-148; covariances and the system of
+ * core/kriging.h:23-135) on a device (device < 0 = current): weights = first n_sources rows of A^-1 B, A^-1 by LU
+ * on the host, both products by the fixed-order fp64 kernel of kernels/ok.hip (no rocBLAS), so the result is
+ * bit-identical to shyft_hip_ordinary_kriging_host. NaN observations are not filtered: a NaN makes its step NaN.
+ * ok_param: c, a, z_scale, cov_type (0 GAUSSIAN, 1 EXPONENTIAL), dst_block (0 = default; else destinations
+ * per pass, a test and measurement aid). src_values [n][n_sources] on the model axis; out [n][n_dst], host.
+ * One source is copied to every destination without a device call (api_interpolation.cpp:141-146); n == 0 or
+ * n_dst == 0 returns 0. Errors carry the reference's texts (api_interpolation.cpp:88-93) or
+ * "inv(): matrix is singular". */
+int shyft_hip_ordinary_kriging(int device, size_t n_sources, const double* src_xyz, const double* src_values, size_t n,
+                               const double* ok_param, size_t n_dst, const double* dst_xyz, double* out);
+/* The same arithmetic on the host, no device call: the restatement the device path is bit-identical to
+ * (api_interpolation.cpp:86-148, core/kriging.h:23-135). */
+int shyft_hip_ordinary_kriging_host(size_t n_sources, const double* src_xyz, const double* src_values, size_t n,
+                                    const double* ok_param, size_t n_dst, const double* dst_xyz, double* out);
+/* Measurement aid of tools/ok_bench.py (no reference counterpart): the three kernels of the ordinary-kriging
+ * path (api_interpolation.cpp:86-148) on generated inputs of n_sources sources, n steps and n_dst destinations,
+ * timed with HIP events, and rocBLAS dgemm on the same two product shapes (the calls kernels/btk.hip makes).
+ * out_ms[6], best of `reps` passes: covariance, weights product, values product (each summed over the blocks of
+ * dst_block destinations, 0 = default), dgemm weights shape, dgemm values shape, and the largest absolute
+ * difference between the two paths' values. */
+int shyft_hip_ok_bench(int device, size_t n_sources, size_t n, size_t n_dst, size_t dst_block, int reps,
+                       double* out_ms);
+
 /* Deterministic synthetic forcing for steps [step0, step0+n) of the resident window,
  * generated on device (bench/test workload; SURVEY.md §8d generator). */
 int shyft_hip_synthetic_forcing(shyft_hip_region* h, uint64_t seed, uint64_t cell_offset, size_t step0, size_t n);

@@ -21,7 +21,7 @@ from ._api import (  # noqa: F401  (re-exported names)
     GeoPoint, LandTypeFractions, RoutingInfo, GeoCellData, TimeAxisFixedDeltaT, point_interpretation_policy,
     POINT_INSTANT_VALUE, POINT_AVERAGE_VALUE, IDWParameter, IDWTemperatureParameter, IDWPrecipitationParameter,
     InterpolationParameter, UHGParameter, River, RiverNetwork, make_uhg_from_gamma, average_values, FlowAdjustResult,
-    find_min_single_variable, BTKParameter,
+    find_min_single_variable, BTKParameter, OKCovarianceType, OKParameter, GAUSSIAN, EXPONENTIAL,
 )
 from . import _api
 
@@ -197,29 +197,45 @@ class _GeoPointSource:
         return g
 
 
-class TemperatureSource(_GeoPointSource):
+class GeoPointSource(_GeoPointSource):
+    """api.GeoPointSource (api/api.h:78-96): a geo-located series; the typed sources derive from it."""
+
+    @property
+    def mid_point_(self):
+        return self._mid_point
+
+    @mid_point_.setter
+    def mid_point_(self, p):
+        self._mid_point = p
+
+
+class TemperatureSource(GeoPointSource):
     pass
 
 
-class PrecipitationSource(_GeoPointSource):
+class PrecipitationSource(GeoPointSource):
     pass
 
 
-class RadiationSource(_GeoPointSource):
+class RadiationSource(GeoPointSource):
     pass
 
 
-class WindSpeedSource(_GeoPointSource):
+class WindSpeedSource(GeoPointSource):
     pass
 
 
-class RelHumSource(_GeoPointSource):
+class RelHumSource(GeoPointSource):
     pass
 
 
 class _SourceVector(_Vector):
     def values_at_time(self, t):
         return DoubleVector(s.ts(t) for s in self)
+
+
+class GeoPointSourceVector(_SourceVector):
+    pass
 
 
 class TemperatureSourceVector(_SourceVector):
@@ -255,6 +271,18 @@ def bayesian_kriging_temperature(src, dst, time_axis, btk_parameter):
     out = TemperatureSourceVector()
     for d, gp in enumerate(dst):
         out.append(TemperatureSource(gp, TimeSeries(time_axis, values[:, d], POINT_AVERAGE_VALUE)))
+    return out
+
+
+def ordinary_kriging(src, dst, time_axis, parameter):
+    """Ordinary kriging of the sources onto the destination points over time_axis
+    (api/boostpython/api_interpolation.cpp:86-148), computed on the MI355X (shyft_hip_ordinary_kriging).
+    src is a GeoPointSourceVector or any of the typed source vectors; NaN observations are not filtered.
+    Returns a GeoPointSourceVector, one source per destination point."""
+    values = _api._ordinary_kriging([s._impl() for s in (src or [])], list(dst or []), time_axis, parameter)
+    out = GeoPointSourceVector()
+    for d, gp in enumerate(dst):
+        out.append(GeoPointSource(gp, TimeSeries(time_axis, values[:, d], POINT_AVERAGE_VALUE)))
     return out
 
 

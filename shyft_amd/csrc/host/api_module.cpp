@@ -357,6 +357,51 @@ PYBIND11_MODULE(_api, m) {
         }
         return py::array_t<double>({T, D}, out.data());
     });
+    // OKCovarianceType, OKParameter (api_interpolation.cpp:73-84, 149-162)
+    py::enum_<ok_covariance_type>(m, "OKCovarianceType", py::arithmetic())
+        .value("GAUSSIAN", ok_covariance_type::GAUSSIAN)
+        .value("EXPONENTIAL", ok_covariance_type::EXPONENTIAL)
+        .export_values();
+    py::class_<ok_parameter>(m, "OKParameter")
+        .def(py::init([](double c, double a, ok_covariance_type cov_type, double z_scale) {
+                 return ok_parameter{c, a, z_scale, cov_type};
+             }),
+             py::arg("c") = 1.0, py::arg("a") = 10 * 1000.0, py::arg("cov_type") = ok_covariance_type::EXPONENTIAL,
+             py::arg("z_scale") = 1.0)
+        .def_readwrite("c", &ok_parameter::c)
+        .def_readwrite("a", &ok_parameter::a)
+        .def_readwrite("cov_type", &ok_parameter::cov_type)
+        .def_readwrite("z_scale", &ok_parameter::z_scale);
+    // ordinary_kriging (api_interpolation.cpp:86-148): validate_parameters' checks, sources averaged onto the axis,
+    // then shyft_hip_ordinary_kriging (its parameter checks, the single-source copy, else the device path)
+    m.def("_ordinary_kriging", [](const std::vector<geo_point_ts>& src, const std::vector<geo_point>& dst,
+                                  const fixed_dt& ta, const ok_parameter& p) {
+        if (src.empty() || dst.empty())
+            throw std::runtime_error("the supplied src and dst_points should be non-null and have at least one time-series");
+        if (ta.size() == 0 || ta.dt == 0)
+            throw std::runtime_error("the supplied destination time-axis should have more than 0 element, and a delta-t larger than 0");
+        const size_t S = src.size(), T = ta.size(), D = dst.size();
+        std::vector<double> xyz(3 * S), vals(T * S), dxyz(3 * D), out(T * D);
+        for (size_t s = 0; s < S; ++s) {
+            xyz[3 * s] = src[s].mid_point.x;
+            xyz[3 * s + 1] = src[s].mid_point.y;
+            xyz[3 * s + 2] = src[s].mid_point.z;
+            auto v = average_values(src[s].ts, ta);
+            for (size_t t = 0; t < T; ++t) vals[t * S + s] = v[t];
+        }
+        for (size_t d = 0; d < D; ++d) {
+            dxyz[3 * d] = dst[d].x;
+            dxyz[3 * d + 1] = dst[d].y;
+            dxyz[3 * d + 2] = dst[d].z;
+        }
+        const double prm[5] = {p.c, p.a, p.z_scale, double(int(p.cov_type)), 0.0};
+        {
+            py::gil_scoped_release nogil;
+            throw_if(shyft_hip_ordinary_kriging(-1, S, xyz.data(), vals.data(), T, prm, D, dxyz.data(), out.data()),
+                     nullptr);
+        }
+        return py::array_t<double>({T, D}, out.data());
+    });
     py::class_<interpolation_parameter>(m, "InterpolationParameter")
         .def(py::init<>())
         .def(py::init([](const btk_parameter& t, const idw_precipitation_parameter& p, const idw_parameter& ws,

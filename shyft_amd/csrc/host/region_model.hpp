@@ -139,6 +139,13 @@ struct btk_parameter {
     void as_abi(double* p) const { p[0] = gradient_sd; p[1] = sill_value; p[2] = nug_value; p[3] = range_value; p[4] = zscale_value; }
 };
 
+// ok_covariance_type, ok_parameter (api/boostpython/api_interpolation.cpp:73-84)
+enum ok_covariance_type { GAUSSIAN = 0, EXPONENTIAL = 1 };
+struct ok_parameter {
+    double c = 1.0, a = 10 * 1000.0, z_scale = 1.0;
+    ok_covariance_type cov_type = ok_covariance_type::EXPONENTIAL;
+};
+
 struct interpolation_parameter {
     bool use_idw_for_temperature = false;
     btk_parameter temperature;

@@ -235,3 +235,34 @@ struct btk_args {
     size_t ld_out;
 };
 void btk_run(const btk_args& a, hipStream_t stream);
+
+// Ordinary kriging engine (kernels/ok.hip; api/boostpython/api_interpolation.cpp:86-148, core/kriging.h:23-135).
+// ok_run: host inputs are read synchronously, A^-1 is made on the host, and per block of dst_block destinations
+// the covariance, weights and values kernels run on `stream`; the result is complete on `stream` on return.
+// ok_host_run: the same arithmetic on the host (no device call), which ok_run is bit-identical to. Both need
+// n_sources >= 2 and throw std::runtime_error with a text ("inv(): matrix is singular" for a singular system).
+struct ok_args {
+    size_t n_sources;
+    const double* src_xyz;     // host [S][3]
+    const double* src_values;  // host [n_steps][S]; NaN is not filtered (a NaN makes its whole step NaN)
+    size_t n_steps;
+    double c, a, z_scale;      // sill, practical range, vertical scale
+    int cov_type;              // 0 GAUSSIAN c exp(-3 h^2 / a^2), 1 EXPONENTIAL c exp(-3 h / a)
+    size_t dst_block;          // destinations per pass, 0 = ok_default_dst_block()
+    size_t n_dst;
+    const double* dst_xyz;     // host [D][3] (ok_host_run)
+    const double* d_dst_xyz;   // device [D][3] (ok_run)
+    double* d_out;             // device: step t, destination d -> d_out[t * ld_out + d] (ok_run)
+    size_t ld_out;
+};
+void ok_run(const ok_args& a, hipStream_t stream);
+void ok_host_run(const ok_args& a, double* out);  // out host [n_steps][n_dst]
+size_t ok_default_dst_block();
+// The two kernels on their own (ok_run's steps; the measurement entry times them one by one).
+// B ((n_src+1) x n_dst, ld ldb) = covariances over a row of ones; k = -3/a (EXPONENTIAL) or -3/a^2 (GAUSSIAN).
+hipError_t launch_ok_cov(const double* d_src_xyz, int n_src, const double* d_dst_xyz, int n_dst, double c, double k,
+                         double z_scale, int gaussian, double* d_B, size_t ldb, hipStream_t stream);
+// C (rows x m, ld ldc) = L R in fixed order, with L given k-major: d_Lt is K x ldl, ldl >= ok_product_ldl(rows).
+int ok_product_ldl(int rows);
+hipError_t launch_ok_product(const double* d_Lt, int ldl, int rows, const double* d_R, size_t ldr, int K, int m,
+                             double* d_C, size_t ldc, hipStream_t stream);

@@ -1068,6 +1068,84 @@ int shyft_hip_btk(int device, size_t n_sources, const double* src_xyz, const dou
     }
 }
 
+// ordinary_kriging's parameter checks and its single-source copy (api_interpolation.cpp:88-93, 141-146), shared by
+// the device and the host entry. Returns true when `out` is already complete.
+static bool ok_prepare(size_t n_sources, const double* src_values, size_t n, const double* ok_param, size_t n_dst,
+                       double* out, ok_args& a) {
+    if (n_sources == 0)
+        throw std::runtime_error("the supplied src and dst_points should be non-null and have at least one time-series");
+    if (!(ok_param[1] > 0.0))
+        throw std::runtime_error("the supplied parameter a, covariance practical range, must be >0.0");
+    if (!(ok_param[0] > 0.0)) throw std::runtime_error("the supplied parameter c, covariance sill, must be >0.0");
+    if (!(ok_param[2] >= 0.0))
+        throw std::runtime_error("the supplied parameter z_scale used to scale vertical distance must be >= 0.0");
+    if (ok_param[3] != 0.0 && ok_param[3] != 1.0)
+        throw std::runtime_error("ordinary_kriging: cov_type must be 0 (GAUSSIAN) or 1 (EXPONENTIAL)");
+    if (!(ok_param[4] >= 0.0)) throw std::runtime_error("ordinary_kriging: dst_block must be >= 0");
+    if (n == 0 || n_dst == 0) return true;
+    if (n_sources == 1) {
+        for (size_t t = 0; t < n; ++t)
+            for (size_t d = 0; d < n_dst; ++d) out[t * n_dst + d] = src_values[t];
+        return true;
+    }
+    a.n_sources = n_sources;
+    a.src_values = src_values;
+    a.n_steps = n;
+    a.c = ok_param[0];
+    a.a = ok_param[1];
+    a.z_scale = ok_param[2];
+    a.cov_type = int(ok_param[3]);
+    a.dst_block = size_t(ok_param[4]);
+    a.n_dst = n_dst;
+    return false;
+}
+
+int shyft_hip_ordinary_kriging(int device, size_t n_sources, const double* src_xyz, const double* src_values, size_t n,
+                               const double* ok_param, size_t n_dst, const double* dst_xyz, double* out) {
+    if (!src_xyz || !src_values || !ok_param || !dst_xyz || !out)
+        return fail(nullptr, "shyft_hip_ordinary_kriging: null argument");
+    try {
+        ok_args a{};
+        if (ok_prepare(n_sources, src_values, n, ok_param, n_dst, out, a)) return 0;
+        if (device >= 0) hip_check(hipSetDevice(device), "hipSetDevice");
+        hipStream_t s = nullptr;
+        hip_check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
+        std::unique_ptr<std::remove_pointer<hipStream_t>::type, void (*)(hipStream_t)> stream(
+            s, [](hipStream_t x) { (void)hipStreamDestroy(x); });
+        dbuf<double> d_xyz, d_out;
+        d_xyz.alloc(3 * n_dst);
+        d_out.alloc(n * n_dst);
+        hip_check(hipMemcpyAsync(d_xyz.p, dst_xyz, 3 * n_dst * sizeof(double), hipMemcpyHostToDevice, s), "upload");
+        a.src_xyz = src_xyz;
+        a.dst_xyz = dst_xyz;
+        a.d_dst_xyz = d_xyz.p;
+        a.d_out = d_out.p;
+        a.ld_out = n_dst;
+        ok_run(a, s);
+        hip_check(hipMemcpyAsync(out, d_out.p, n * n_dst * sizeof(double), hipMemcpyDeviceToHost, s), "download");
+        hip_check(hipStreamSynchronize(s), "sync");
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(nullptr, e.what());
+    }
+}
+
+int shyft_hip_ordinary_kriging_host(size_t n_sources, const double* src_xyz, const double* src_values, size_t n,
+                                    const double* ok_param, size_t n_dst, const double* dst_xyz, double* out) {
+    if (!src_xyz || !src_values || !ok_param || !dst_xyz || !out)
+        return fail(nullptr, "shyft_hip_ordinary_kriging_host: null argument");
+    try {
+        ok_args a{};
+        if (ok_prepare(n_sources, src_values, n, ok_param, n_dst, out, a)) return 0;
+        a.src_xyz = src_xyz;
+        a.dst_xyz = dst_xyz;
+        ok_host_run(a, out);
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(nullptr, e.what());
+    }
+}
+
 int shyft_hip_synthetic_elevation(uint64_t seed, uint64_t cell_offset, size_t n_cells, double* z_host) {
     if (!z_host) return fail(nullptr, "shyft_hip_synthetic_elevation: null argument");
     for (size_t i = 0; i < n_cells; ++i) z_host[i] = synth_elevation(seed, cell_offset + i);

@@ -369,3 +369,25 @@ def btk(src_xyz, src_values, prior_gradient, btk_param, dst_xyz, device: int = -
     check(L.shyft_hip_btk(device, xyz.shape[0], _ptr(xyz), _ptr(v), v.shape[0], _ptr(g), _ptr(p), d.shape[0],
                           _ptr(d), _ptr(out)), None)
     return out
+
+
+def ordinary_kriging(src_xyz, src_values, ok_param, dst_xyz, device: int = -1, host: bool = False,
+                     dst_block: int = 0) -> np.ndarray:
+    """Stateless ordinary kriging (shyft_hip_ordinary_kriging): src_values [n][S] on the model axis, ok_param
+    (c, a, z_scale, cov_type 0 GAUSSIAN / 1 EXPONENTIAL), dst_xyz [D][3] -> [n][D]. host=True evaluates the same
+    arithmetic on the host (shyft_hip_ordinary_kriging_host), which the device result is bit-identical to;
+    dst_block sets the destinations per device pass (0 = default)."""
+    L = lib()
+    xyz = np.ascontiguousarray(src_xyz, dtype=np.float64).reshape(-1, 3)
+    v = np.ascontiguousarray(src_values, dtype=np.float64).reshape(-1, xyz.shape[0]) if xyz.shape[0] else \
+        np.empty((0, 0))
+    p = np.append(np.asarray(ok_param, dtype=np.float64).reshape(4), float(dst_block))
+    d = np.ascontiguousarray(dst_xyz, dtype=np.float64).reshape(-1, 3)
+    out = np.empty((v.shape[0], d.shape[0]))
+    if host:
+        check(L.shyft_hip_ordinary_kriging_host(xyz.shape[0], _ptr(xyz), _ptr(v), v.shape[0], _ptr(p), d.shape[0],
+                                                _ptr(d), _ptr(out)), None)
+    else:
+        check(L.shyft_hip_ordinary_kriging(device, xyz.shape[0], _ptr(xyz), _ptr(v), v.shape[0], _ptr(p), d.shape[0],
+                                           _ptr(d), _ptr(out)), None)
+    return out
