@@ -289,6 +289,49 @@ int shyft_hip_catchment_sums(const shyft_hip_region* h, int series, size_t step0
  * (optimizer::extract_area_ts_property, core/model_calibration.h:759-776). dst[n_catchments][n]. */
 int shyft_hip_catchment_area_sums(const shyft_hip_region* h, int series, size_t step0, size_t n, double* dst,
                                   int dst_on_device);
+
+/* Percentiles across cells (calculate_percentiles with skip_nans, core/time_series_statistics.h:112-246, the
+ * api.percentiles / TsVector.percentiles of api/boostpython/api_time_series.cpp, taken over the cells of a region on
+ * its own time axis). For every step the samples are the finite values of the selected cells; pct[k] is
+ *   0..100   the R7 percentile as the reference evaluates it (:133-153, with its eps = 1e-30 rules),
+ *   -1       AVERAGE: the mean of the samples (:127-132),
+ *   -1000 / +1000  MIN_EXTREME / MAX_EXTREME: the smallest / largest sample (one value per series and interval,
+ *            so extract_statistic_from_vector with nan_min / nan_max, :25-39, :77-90, :221-226, is that),
+ *   anything else, or no finite sample: NaN.
+ * Order statistics are exact: every entry but AVERAGE is bit-identical to shyft_hip_percentiles_host (the sign of
+ * a zero result is unspecified, as +0.0 and -0.0 compare equal in a sort); AVERAGE is a fixed-order sum, reproducible
+ * run to run, that differs from the host's sorted sequential sum by rounding only. n_pct is at most
+ * SHYFT_HIP_PERCENTILES_MAX; n_pct == 0 returns 0 and writes nothing. A segment (the selection, or a catchment) of at
+ * most SHYFT_HIP_PERCENTILES_LDS_MAX cells is sorted in LDS by one workgroup per step; a call with a larger segment
+ * runs a radix select over the 64-bit keys of the values (kernels/percentiles.hip). A sharded region returns an
+ * error ("percentiles: not available for a sharded region"). */
+#define SHYFT_HIP_PERCENTILES_MAX 16
+#define SHYFT_HIP_PERCENTILES_LDS_MAX 4096
+enum shyft_hip_statistics_property {
+    SHYFT_HIP_STAT_AVERAGE = -1, SHYFT_HIP_STAT_MIN_EXTREME = -1000, SHYFT_HIP_STAT_MAX_EXTREME = 1000
+};
+/* Series ids, selection (ids[n_ids], scope; n_ids == 0 selects all cells), window and unknown-id errors as
+ * shyft_hip_statistics. dst is host [n_pct][n]. A selection that matches no cell gives NaN. */
+int shyft_hip_percentiles(const shyft_hip_region* h, int series, const int64_t* ids, size_t n_ids, int scope,
+                          const int64_t* pct, size_t n_pct, size_t step0, size_t n, double* dst);
+/* The same for every catchment in one call: dst[n_catchments][n_pct][n] in catchment_ids() order, device or host. */
+int shyft_hip_catchment_percentiles(const shyft_hip_region* h, int series, const int64_t* pct, size_t n_pct,
+                                    size_t step0, size_t n, double* dst, int dst_on_device);
+/* The host restatement, no device call (time_series_statistics.h:115-160): rows [n_steps][n_samples_per_step], the
+ * non-finite samples of a step dropped, a full sort per step, AVERAGE summed sequentially over the sorted samples.
+ * dst [n_pct][n_steps]; n_pct is not limited here. */
+int shyft_hip_percentiles_host(const double* rows, size_t n_steps, size_t n_samples_per_step, const int64_t* pct,
+                               size_t n_pct, double* dst);
+/* Which path the last percentile call of this region took (no reference counterpart: a test and measurement aid):
+ * SHYFT_HIP_PERCENTILES_NONE (none yet, or nothing was launched), _LDS_SORT, _RADIX. Returns -1 on a bad handle. */
+enum shyft_hip_percentiles_path_id {
+    SHYFT_HIP_PERCENTILES_NONE = 0, SHYFT_HIP_PERCENTILES_LDS_SORT = 1, SHYFT_HIP_PERCENTILES_RADIX = 2
+};
+int shyft_hip_percentiles_path(const shyft_hip_region* h);
+/* Milliseconds of the last percentile call's kernels, first launch to last, timed with HIP events on the region's
+ * stream; uploads and the copy of the result are not included. (No reference counterpart: measurement only.) */
+double shyft_hip_last_percentiles_ms(const shyft_hip_region* h);
+
 size_t shyft_hip_number_of_catchments(const shyft_hip_region* h);
 int shyft_hip_catchment_ids(const shyft_hip_region* h, int64_t* cids);
 
@@ -320,7 +363,10 @@ enum shyft_hip_knob {
     /* sharded regions: k >= 0 makes the next shyft_hip_region_clone of this region fail when it reaches shard k (the
      * shards before it already cloned, with their streams), so the clean-up of a partly built clone is exercised;
      * the failure is reported like any other and disarms the knob; < 0 = off (the default) */
-    SHYFT_HIP_KNOB_CLONE_FAIL_AT = 4
+    SHYFT_HIP_KNOB_CLONE_FAIL_AT = 4,
+    /* percentiles: 0 = the launcher picks the path by segment size, 1 = LDS sort (a call with a segment of more than
+     * SHYFT_HIP_PERCENTILES_LDS_MAX cells then fails), 2 = radix select */
+    SHYFT_HIP_KNOB_PERCENTILES_PATH = 5
 };
 int shyft_hip_set_test_knob(shyft_hip_region* h, int knob, int64_t value);
 

@@ -72,6 +72,13 @@ SIGNATURES = {
                                        C.c_void_p]),
     "shyft_hip_catchment_sums": (C.c_int, [_h, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int]),
     "shyft_hip_catchment_area_sums": (C.c_int, [_h, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int]),
+    "shyft_hip_percentiles": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.c_size_t, C.c_size_t, C.c_void_p]),
+    "shyft_hip_catchment_percentiles": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                  C.c_void_p, C.c_int]),
+    "shyft_hip_percentiles_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "shyft_hip_percentiles_path": (C.c_int, [_h]),
+    "shyft_hip_last_percentiles_ms": (C.c_double, [_h]),
     "shyft_hip_number_of_catchments": (C.c_size_t, [_h]),
     "shyft_hip_catchment_ids": (C.c_int, [_h, C.c_void_p]),
     "shyft_hip_region_clone": (C.c_int, [_h, C.POINTER(C.c_void_p)]),

@@ -170,6 +170,86 @@ class TimeSeries:
         return TimeSeries(ta, self._ts.average(ta), POINT_AVERAGE_VALUE)
 
 
+# ---- percentiles of a set of series (core/time_series_statistics.h:107-246; api_time_series.cpp) ---------------------
+class statistics_property:  # time_series_statistics.h:107-111
+    AVERAGE = -1
+    MIN_EXTREME = -1000
+    MAX_EXTREME = 1000
+
+
+def _extract_statistics(ts, ta, fx):
+    """extract_statistics (time_series_statistics.h:41-75): fx folded over the points of ts inside each interval of ta."""
+    times, vals = ts._ts._times, ts._ts._values
+    n = len(times)
+    t_first = ta.time(0) if ta.size() else 0.0
+    i_s = None  # make_time_axis_map(ts.time_axis(), ta).src_index(0)
+    if n and times[0] <= t_first < ts._ts._t_end:
+        i_s = int(np.searchsorted(np.asarray(times), t_first, side="right")) - 1
+    r = []
+    for i in range(ta.size()):
+        p0, p1 = ta.period(i)
+        rv = float("nan")
+        if i_s is None:
+            if n and p0 <= times[0] < p1:
+                i_s = 0
+            else:
+                r.append(rv)
+                continue
+        if i_s < n and times[i_s] < p0:
+            i_s += 1
+        while i_s < n and times[i_s] < p1:
+            rv = fx(rv, float(vals[i_s]))
+            i_s += 1
+        r.append(rv)
+    return r
+
+
+def _nan_fold(pick):
+    """nan_min / nan_max (time_series_statistics.h:24-39): the fold ignores non-finite values."""
+    def fx(r, x):
+        if not np.isfinite(x):
+            return r
+        if not np.isfinite(r):
+            return x
+        return pick(r, x)
+    return fx
+
+
+def percentiles(ts_vector, time_axis, percentiles):
+    """api.percentiles (calculate_percentiles, time_series_statistics.h:184-246), on the host: every series goes
+    through its true average onto time_axis, non-finite samples are dropped, and each entry of `percentiles` (0..100 by
+    R7, statistics_property.AVERAGE, MIN_EXTREME / MAX_EXTREME) gives one series; the extremes are the true extremes
+    of the points inside each interval. The results carry the point interpretation of the first series."""
+    from ..region import percentiles_host
+    tsv, pcts = list(ts_vector), [int(p) for p in percentiles]
+    fx_p = tsv[0].point_interpretation() if tsv else POINT_AVERAGE_VALUE
+    n = time_axis.size()
+    samples = np.empty((n, len(tsv)))
+    for k, ts in enumerate(tsv):
+        samples[:, k] = np.asarray(ts.average(time_axis)._ts._values)
+    values = percentiles_host(samples, pcts) if n and pcts else np.empty((len(pcts), n))
+    out = TsVector()
+    for k, p in enumerate(pcts):
+        v = values[k]
+        if p in (statistics_property.MIN_EXTREME, statistics_property.MAX_EXTREME):
+            fx = _nan_fold(min if p == statistics_property.MIN_EXTREME else max)
+            v = [float("nan")] * n
+            for ts in tsv:  # extract_statistic_from_vector (:77-90)
+                v = [fx(a, b) for a, b in zip(v, _extract_statistics(ts, time_axis, fx))]
+        out.append(TimeSeries(time_axis, v, fx_p))
+    return out
+
+
+_percentiles_of = percentiles  # the method below has a parameter of the function's name
+
+
+class TsVector(_Vector):
+    """api.TsVector: a vector of TimeSeries (api_time_series.cpp)."""
+
+    def percentiles(self, time_axis, percentiles):
+        return _percentiles_of(self, time_axis, percentiles)
+
+
 class TsFactory:
     """api.TsFactory (api/api.h:1630-1700)."""
 
@@ -576,10 +656,23 @@ class _Statistics:
             ta = TimeAxisFixedDeltaT(ta.start, ta.delta_t, ta.size() + 1)
         return TimeSeries(ta, v, POINT_AVERAGE_VALUE)
 
+    def _percentiles(self, sid, indexes, percentiles, ix_type):
+        """<name>_percentiles: percentiles across the selected cells per step, selected on the device
+        (calculate_percentiles, core/time_series_statistics.h:112-246), one series per entry of `percentiles`."""
+        v = self._m._percentiles(sid, list(indexes), int(ix_type), [int(p) for p in percentiles])
+        ta = self._m._time_axis
+        if sid >= SERIES_STATE:
+            ta = TimeAxisFixedDeltaT(ta.start, ta.delta_t, ta.size() + 1)
+        return TsVector(TimeSeries(ta, row, POINT_AVERAGE_VALUE) for row in v)
+
     def __getattr__(self, name):
         if name.startswith("_"):
             raise AttributeError(name)
         spec = self._spec
+        if name.endswith("_percentiles") and name[:-12] in spec and spec[name[:-12]][0] != "pot_ratio":
+            sid = spec[name[:-12]][0]
+            return lambda indexes, percentiles, ix_type=stat_scope.catchment: self._percentiles(sid, indexes, percentiles,
+                                                                                                 ix_type)
         if name.endswith("_value") and name[:-6] in spec:
             sid, w = spec[name[:-6]]
             if sid == "pot_ratio":
@@ -756,6 +849,17 @@ class _ModelMixin:
 
     def catchment_charges(self):
         return [TimeSeries(self._time_axis, v, POINT_AVERAGE_VALUE) for v in self._catchment_sums(1)]
+
+    def catchment_percentiles(self, series, percentiles):
+        """Percentiles across the cells of every catchment in one device call (no reference counterpart: the
+        per-catchment form of statistics.<name>_percentiles): a list, in catchment_ids order, of TsVector with one
+        series per entry of `percentiles`. series: a response series name of the stack, or its id."""
+        sid = self._SERIES.index(series) if isinstance(series, str) else int(series)
+        ta = self._time_axis
+        if sid >= SERIES_STATE:
+            ta = TimeAxisFixedDeltaT(ta.start, ta.delta_t, ta.size() + 1)
+        v = self._catchment_percentiles(sid, [int(p) for p in percentiles])
+        return [TsVector(TimeSeries(ta, row, POINT_AVERAGE_VALUE) for row in c) for c in v]
 
 
 class _RiverNetworkProxy:

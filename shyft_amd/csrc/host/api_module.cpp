@@ -91,6 +91,19 @@ void bind_model(py::module_& m, const char* name) {
             auto v = x.stat_series(s, ids, scope, w);
             return py::array_t<double>(v.size(), v.data());
         })
+        .def("_percentiles", [](const M& x, int s, const std::vector<int64_t>& ids, int scope,
+                                const std::vector<int64_t>& pcts) {
+            auto v = x.percentiles(s, ids, scope, pcts);
+            py::array_t<double> a({pcts.size(), x.series_length(s)});
+            std::copy(v.begin(), v.end(), a.mutable_data());
+            return a;
+        })
+        .def("_catchment_percentiles", [](const M& x, int s, const std::vector<int64_t>& pcts) {
+            auto v = x.catchment_percentiles(s, pcts);
+            py::array_t<double> a({x.number_of_catchments(), pcts.size(), x.series_length(s)});
+            std::copy(v.begin(), v.end(), a.mutable_data());
+            return a;
+        })
         .def("_stat_value", &M::stat_value)
         .def("_stat_raster", &M::stat_raster)
         .def("_pot_ratio_series", [](const M& x, const std::vector<int64_t>& ids, int scope) {

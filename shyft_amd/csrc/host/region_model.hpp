@@ -642,6 +642,24 @@ class region_model {
                  h_.get());
         return r;
     }
+    // percentiles across the selected cells per step, on the device (calculate_percentiles with skip_nans,
+    // core/time_series_statistics.h:112-246; pcts as statistics_property :107-111): flat [pcts][series_length]
+    std::vector<double> percentiles(int series, const std::vector<int64_t>& ids, int scope,
+                                    const std::vector<int64_t>& pcts) const {
+        const size_t n = series_length(series);
+        std::vector<double> r(pcts.size() * n);
+        throw_if(shyft_hip_percentiles(h_.get(), series, ids.empty() ? nullptr : ids.data(), ids.size(), scope,
+                                       pcts.data(), pcts.size(), 0, n, r.data()),
+                 h_.get());
+        return r;
+    }
+    // the same for every catchment in one call: flat [catchment][pcts][series_length], catchment_ids() order
+    std::vector<double> catchment_percentiles(int series, const std::vector<int64_t>& pcts) const {
+        const size_t n = series_length(series);
+        std::vector<double> r(number_of_catchments() * pcts.size() * n);
+        throw_if(shyft_hip_catchment_percentiles(h_.get(), series, pcts.data(), pcts.size(), 0, n, r.data(), 0), h_.get());
+        return r;
+    }
     // catchment_feature: the i'th value of every selected cell (cell_model.h:340-366)
     std::vector<double> stat_raster(int series, const std::vector<int64_t>& ids, int scope, size_t i) const {
         auto sel = select(ids, scope);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../../include/shyft_hip.h"
 #include "layout.h"
 
 struct ptgsk_kargs {
@@ -140,6 +141,22 @@ hipError_t launch_select_sum(const double* series, size_t n_cells, size_t n_step
 hipError_t launch_segment_sums(const double* series, size_t n_cells, size_t n_steps, const int32_t* seg_cells,
                                const int32_t* seg_off, size_t n_seg, double* out, hipStream_t stream,
                                const double* w = nullptr);
+// cell percentiles (kernels/percentiles.hip; calculate_percentiles, core/time_series_statistics.h:112-246):
+// out[seg][pct][t] over the finite values of series[t][seg_cells[seg_off[seg]..seg_off[seg+1])] (seg_cells == null:
+// the identity). path is SHYFT_HIP_PERCENTILES_LDS_SORT (max_count, the largest segment, must not exceed
+// SHYFT_HIP_PERCENTILES_LDS_MAX) or SHYFT_HIP_PERCENTILES_RADIX, which works in batches of
+// ws_bytes / percentiles_job_bytes(n_pct) (segment, step) jobs in the device workspace ws.
+struct pct_list {
+    int64_t p[SHYFT_HIP_PERCENTILES_MAX];
+    int n;
+};
+size_t percentiles_job_bytes(int n_pct);
+hipError_t launch_percentiles(const double* series, size_t n_cells, size_t n_steps, const int32_t* seg_cells,
+                              const int32_t* seg_off, size_t n_seg, size_t max_count, const pct_list& pl, int path,
+                              void* ws, size_t ws_bytes, double* out, hipStream_t stream);
+// the same on the host, no device call: rows [n_steps][n_per_step] -> dst [n_pct][n_steps]
+void percentiles_host(const double* rows, size_t n_steps, size_t n_per_step, const int64_t* pct, size_t n_pct,
+                      double* dst);
 // sharded regions: a shard's [n_rows][n] partials into rows[r] of the region's [R][n]; S partials [S][M] added in
 // shard order
 hipError_t launch_scatter_rows(const double* src, const int32_t* rows, size_t n_rows, size_t n, double* dst,

@@ -67,6 +67,10 @@ struct shyft_hip_region {
     double last_ms = 0.0;
     double last_interp_ms = 0.0;  // the last interpolate's gather kernel
     int knob_instance = 0, knob_read_delay = 0;  // shyft_hip_set_test_knob (pt_gs_k launches)
+    int knob_pct_path = 0;                       // SHYFT_HIP_KNOB_PERCENTILES_PATH
+    int pct_path = SHYFT_HIP_PERCENTILES_NONE;   // the path of the last percentile call
+    double last_pct_ms = 0.0;                    // its kernels, first launch to last (HIP events on the stream)
+    hipEvent_t ev_pct0 = nullptr, ev_pct1 = nullptr;
 
     // host mirrors
     std::vector<double> geo;  // n x 11
@@ -104,6 +108,8 @@ struct shyft_hip_region {
     dbuf<double> d_tmp, d_w, d_alt;
     dbuf<int64_t> d_cell_ids;  // a z-balanced shard: the region cell of each of its cells (synthetic forcing keys)
     dbuf<int32_t> d_flag;
+    dbuf<int32_t> d_pct_off;       // percentiles of one selection: its segment table {0, n_selected}
+    dbuf<unsigned char> d_pct_ws;  // radix-select jobs and histograms (kernels/percentiles.hip)
 
     // inverse-distance neighbour tables, one per forcing variable, cached by
     // (model, parameters, source geometry)

@@ -432,6 +432,8 @@ void shyft_hip_region_destroy(shyft_hip_region* h) {
     if (h->gen_stream) (void)hipStreamSynchronize(h->gen_stream);  // a prefetch may still write d_forcing_next
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->ev_pct0) (void)hipEventDestroy(h->ev_pct0);
+    if (h->ev_pct1) (void)hipEventDestroy(h->ev_pct1);
     if (h->ev_gen) (void)hipEventDestroy(h->ev_gen);
     if (h->ev_free) (void)hipEventDestroy(h->ev_free);
     if (h->gen_stream) (void)hipStreamDestroy(h->gen_stream);
@@ -1490,6 +1492,133 @@ int shyft_hip_catchment_area_sums(const shyft_hip_region* hc, int series, size_t
     });
 }
 
+}  // extern "C"
+namespace {
+
+constexpr size_t PCT_WS_MAX = size_t(128) << 20;  // radix-select workspace cap: larger calls run in batches of jobs
+
+pct_list percentile_list(const int64_t* pct, size_t n_pct) {
+    if (n_pct > size_t(SHYFT_HIP_PERCENTILES_MAX))
+        throw std::runtime_error("percentiles: " + std::to_string(n_pct) + " percentiles in one call, the maximum is " +
+                                 std::to_string(SHYFT_HIP_PERCENTILES_MAX));
+    pct_list pl{};
+    pl.n = int(n_pct);
+    for (size_t i = 0; i < n_pct; ++i) pl.p[i] = pct[i];
+    return pl;
+}
+
+// out[n_seg][n_pct][n] on the device; max_count = the largest segment. Picks the path (SHYFT_HIP_KNOB_PERCENTILES_PATH).
+void run_percentiles(shyft_hip_region* h, const double* src, size_t n, const int32_t* seg_cells, const int32_t* seg_off,
+                     size_t n_seg, size_t max_count, const pct_list& pl, double* out) {
+    const bool fits = max_count <= size_t(SHYFT_HIP_PERCENTILES_LDS_MAX);
+    if (h->knob_pct_path == SHYFT_HIP_PERCENTILES_LDS_SORT && !fits)
+        throw std::runtime_error("percentiles: the LDS sort path is forced and a segment of " + std::to_string(max_count) +
+                                 " cells does not fit (at most " + std::to_string(SHYFT_HIP_PERCENTILES_LDS_MAX) + ")");
+    const int path = h->knob_pct_path ? h->knob_pct_path : (fits ? SHYFT_HIP_PERCENTILES_LDS_SORT : SHYFT_HIP_PERCENTILES_RADIX);
+    size_t ws = 0;
+    if (path == SHYFT_HIP_PERCENTILES_RADIX) {
+        const size_t per_job = percentiles_job_bytes(pl.n);
+        ws = std::max(per_job, std::min(PCT_WS_MAX, n * n_seg * per_job));
+        if (h->d_pct_ws.n < ws) h->d_pct_ws.alloc(ws);
+        ws = h->d_pct_ws.n;
+    }
+    if (!h->ev_pct0) {  // events of their own: ev0 / ev1 may belong to a run still queued (run_cells_async)
+        hip_check(hipEventCreate(&h->ev_pct0), "hipEventCreate");
+        hip_check(hipEventCreate(&h->ev_pct1), "hipEventCreate");
+    }
+    hip_check(hipEventRecord(h->ev_pct0, h->stream), "hipEventRecord");
+    hip_check(launch_percentiles(src, h->n, n, seg_cells, seg_off, n_seg, max_count, pl, path, h->d_pct_ws.p, ws, out,
+                                 h->stream),
+              "percentiles");
+    hip_check(hipEventRecord(h->ev_pct1, h->stream), "hipEventRecord");
+    hip_check(hipEventSynchronize(h->ev_pct1), "percentiles");
+    float ms = 0.f;
+    hip_check(hipEventElapsedTime(&ms, h->ev_pct0, h->ev_pct1), "hipEventElapsedTime");
+    h->last_pct_ms = ms;
+    h->pct_path = path;
+}
+
+}  // namespace
+extern "C" {
+
+int shyft_hip_percentiles(const shyft_hip_region* hc, int series, const int64_t* ids, size_t n_ids, int scope,
+                          const int64_t* pct, size_t n_pct, size_t step0, size_t n, double* dst) {
+    shyft_hip_region* h = const_cast<shyft_hip_region*>(hc);
+    if (!h) return fail(h, "shyft_hip_percentiles: null argument");
+    if (h->sh) return fail(h, "percentiles: not available for a sharded region");
+    if (n_pct == 0) return 0;
+    if (!pct || !dst) return fail(h, "shyft_hip_percentiles: null argument");
+    return guarded(h, [&] {
+        const pct_list pl = percentile_list(pct, n_pct);
+        const double* src = series_rows(h, series, step0, n, "percentiles");
+        std::vector<int32_t> sel = select_cells(h, ids, n_ids, scope);
+        h->pct_path = SHYFT_HIP_PERCENTILES_NONE;
+        if (n == 0) return;
+        if (sel.empty()) {
+            for (size_t i = 0; i < n_pct * n; ++i) dst[i] = NAN;
+            return;
+        }
+        bool identity = sel.size() == h->n;  // all cells in cell order: the index array is not read
+        for (size_t i = 0; i < sel.size() && identity; ++i) identity = sel[i] == int32_t(i);
+        if (!identity) {
+            h->d_sel.alloc(std::max(h->d_sel.n, sel.size()));
+            hip_check(region_copy(h, h->d_sel.p, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice), "upload sel");
+        }
+        const int32_t off[2] = {0, int32_t(sel.size())};
+        h->d_pct_off.alloc(2);
+        hip_check(region_copy(h, h->d_pct_off.p, off, sizeof(off), hipMemcpyHostToDevice), "upload segment");
+        h->d_tmp.alloc(std::max(h->d_tmp.n, n_pct * n));
+        run_percentiles(h, src, n, identity ? nullptr : h->d_sel.p, h->d_pct_off.p, 1, sel.size(), pl, h->d_tmp.p);
+        copy_rows(h->stream, dst, h->d_tmp.p, n_pct * n * sizeof(double), 0, 1);
+    });
+}
+
+int shyft_hip_catchment_percentiles(const shyft_hip_region* hc, int series, const int64_t* pct, size_t n_pct,
+                                    size_t step0, size_t n, double* dst, int dst_on_device) {
+    shyft_hip_region* h = const_cast<shyft_hip_region*>(hc);
+    if (!h) return fail(h, "shyft_hip_catchment_percentiles: null argument");
+    if (h->sh) return fail(h, "percentiles: not available for a sharded region");
+    if (n_pct == 0) return 0;
+    if (!pct || !dst) return fail(h, "shyft_hip_catchment_percentiles: null argument");
+    return guarded(h, [&] {
+        const pct_list pl = percentile_list(pct, n_pct);
+        const double* src = series_rows(h, series, step0, n, "catchment_percentiles");
+        const size_t C = h->cix_to_cid.size();
+        h->pct_path = SHYFT_HIP_PERCENTILES_NONE;
+        if (n == 0 || C == 0) return;
+        std::vector<size_t> count(C, 0);
+        for (size_t i = 0; i < h->n; ++i) ++count[h->cix[i]];
+        const size_t max_count = *std::max_element(count.begin(), count.end());
+        double* out = dst;
+        if (!dst_on_device) {
+            h->d_tmp.alloc(std::max(h->d_tmp.n, C * n_pct * n));
+            out = h->d_tmp.p;
+        }
+        run_percentiles(h, src, n, h->seg_identity ? nullptr : h->d_seg_cells.p, h->d_seg_off.p, C, max_count, pl, out);
+        if (!dst_on_device) copy_rows(h->stream, dst, out, C * n_pct * n * sizeof(double), 0, 1);
+        else hip_check(hipStreamSynchronize(h->stream), "sync");
+    });
+}
+
+int shyft_hip_percentiles_host(const double* rows, size_t n_steps, size_t n_samples_per_step, const int64_t* pct,
+                               size_t n_pct, double* dst) {
+    if (n_pct == 0 || n_steps == 0) return 0;
+    if (!pct || !dst || (!rows && n_samples_per_step)) return fail(nullptr, "shyft_hip_percentiles_host: null argument");
+    try {
+        percentiles_host(rows, n_steps, n_samples_per_step, pct, n_pct, dst);
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(nullptr, e.what());
+    }
+}
+
+int shyft_hip_percentiles_path(const shyft_hip_region* h) {
+    if (!h) return -1;
+    return h->pct_path;
+}
+
+double shyft_hip_last_percentiles_ms(const shyft_hip_region* h) { return h ? h->last_pct_ms : 0.0; }
+
 size_t shyft_hip_number_of_catchments(const shyft_hip_region* h) {
     return h ? (h->sh ? shards::number_of_catchments(h->sh) : h->cix_to_cid.size()) : 0;
 }
@@ -1609,6 +1738,10 @@ int shyft_hip_set_test_knob(shyft_hip_region* h, int knob, int64_t value) {
         } else if (knob == SHYFT_HIP_KNOB_BRENT_READ_DELAY) {
             if (value < 0 || value > 1000) throw std::runtime_error("set_test_knob: read delay must be in [0, 1000]");
             h->knob_read_delay = int(value);
+        } else if (knob == SHYFT_HIP_KNOB_PERCENTILES_PATH) {
+            if (value < 0 || value > 2)
+                throw std::runtime_error("set_test_knob: percentiles path must be 0 (auto), 1 (LDS sort) or 2 (radix select)");
+            h->knob_pct_path = int(value);
         } else {
             throw std::runtime_error("set_test_knob: unknown knob");
         }

@@ -28,6 +28,11 @@ HBV_STATE = (("swe", "sca", "soil_moisture", "tank_uz", "tank_lz", "n_bins") +
 SCOPE_CELL_IX, SCOPE_CATCHMENT = 0, 1
 SERIES_FORCING, SERIES_STATE = 100, 200
 KNOB_PTGSK_INSTANCE, KNOB_BRENT_READ_DELAY, KNOB_SERIAL_SHARDS, KNOB_CLONE_FAIL_AT = 1, 2, 3, 4
+KNOB_PERCENTILES_PATH = 5  # 0 auto, 1 LDS sort, 2 radix select
+# shyft_hip_percentiles (include/shyft_hip.h): list cap, LDS-sort segment limit, statistics_property, path names
+PERCENTILES_MAX, PERCENTILES_LDS_MAX = 16, 4096
+STAT_AVERAGE, STAT_MIN_EXTREME, STAT_MAX_EXTREME = -1, -1000, 1000
+PERCENTILES_PATHS = ("none", "lds_sort", "radix")
 # shyft_hip_region_create_sharded_ex options (include/shyft_hip.h)
 SHARD_RCCL_ALWAYS, SHARD_NO_RCCL, SHARD_TEST_FAIL_INIT, SHARD_TEST_FAIL_GATHER, SHARD_TEST_CORRUPT_CHECK = 1, 2, 4, 8, 16
 SHARD_BALANCE_Z = 32
@@ -276,6 +281,39 @@ class HipRegion:
                                                int(weighted), step0, n, _ptr(out)))
         return out
 
+    def percentiles(self, series: int, pcts, ids=(), scope: int = SCOPE_CATCHMENT, step0: int = 0,
+                    n: int | None = None) -> np.ndarray:
+        """[len(pcts)][n] percentiles across the selected cells per step (shyft_hip_percentiles): 0..100 R7,
+        STAT_AVERAGE, STAT_MIN_EXTREME / STAT_MAX_EXTREME; non-finite values are dropped."""
+        n = self.n_steps - step0 if n is None else n
+        i = np.ascontiguousarray(list(ids), dtype=np.int64)
+        p = np.ascontiguousarray(list(pcts), dtype=np.int64)
+        out = np.empty((p.size, n), dtype=np.float64)
+        self._chk(self._L.shyft_hip_percentiles(self.h, int(series), _ptr(i) if i.size else None, i.size, int(scope),
+                                                _ptr(p), p.size, int(step0), int(n), _ptr(out)))
+        return out
+
+    def catchment_percentiles(self, series: int, pcts, step0: int, n: int) -> np.ndarray:
+        """[n_catchments][len(pcts)][n], catchments in catchment_ids() order (shyft_hip_catchment_percentiles)."""
+        p = np.ascontiguousarray(list(pcts), dtype=np.int64)
+        out = np.empty((self.number_of_catchments(), p.size, n), dtype=np.float64)
+        self._chk(self._L.shyft_hip_catchment_percentiles(self.h, int(series), _ptr(p), p.size, int(step0), int(n),
+                                                          _ptr(out), 0))
+        return out
+
+    def catchment_percentiles_device(self, series: int, pcts, step0: int, n: int, dev_ptr: int):
+        p = np.ascontiguousarray(list(pcts), dtype=np.int64)
+        self._chk(self._L.shyft_hip_catchment_percentiles(self.h, int(series), _ptr(p), p.size, int(step0), int(n),
+                                                          C.c_void_p(dev_ptr), 1))
+
+    def percentiles_path(self) -> str:
+        """The path of the last percentile call: "none", "lds_sort" or "radix"."""
+        return PERCENTILES_PATHS[int(self._L.shyft_hip_percentiles_path(self.h))]
+
+    def last_percentiles_ms(self) -> float:
+        """The last percentile call's kernels, ms (HIP events on the region's stream)."""
+        return float(self._L.shyft_hip_last_percentiles_ms(self.h))
+
     def number_of_catchments(self) -> int:
         return int(self._L.shyft_hip_number_of_catchments(self.h))
 
@@ -368,6 +406,17 @@ def btk(src_xyz, src_values, prior_gradient, btk_param, dst_xyz, device: int = -
     out = np.empty((v.shape[0], d.shape[0]))
     check(L.shyft_hip_btk(device, xyz.shape[0], _ptr(xyz), _ptr(v), v.shape[0], _ptr(g), _ptr(p), d.shape[0],
                           _ptr(d), _ptr(out)), None)
+    return out
+
+
+def percentiles_host(rows, pcts) -> np.ndarray:
+    """The host restatement of the percentile kernels (shyft_hip_percentiles_host, no device call):
+    rows [n_steps][n_samples] -> [len(pcts)][n_steps]."""
+    r = np.ascontiguousarray(rows, dtype=np.float64)
+    assert r.ndim == 2
+    p = np.ascontiguousarray(list(pcts), dtype=np.int64)
+    out = np.empty((p.size, r.shape[0]), dtype=np.float64)
+    check(lib().shyft_hip_percentiles_host(_ptr(r), r.shape[0], r.shape[1], _ptr(p), p.size, _ptr(out)), None)
     return out
 
 
