@@ -332,6 +332,39 @@ int shyft_hip_percentiles_path(const shyft_hip_region* h);
  * stream; uploads and the copy of the result are not included. (No reference counterpart: measurement only.) */
 double shyft_hip_last_percentiles_ms(const shyft_hip_region* h);
 
+/* Batched Kalman bias filter (core/kalman.h:24-236): M independent filters of size n = n_daily_observations run T
+ * steps of filter::update (kalman.h:127-145) in one launch of kernels/kalman.hip on a device (device < 0 = current).
+ * Host pointers, stateless. Structure-of-arrays, point fastest: bias [T][M]; x [n][M], k [n][M] and P [n*n][M]
+ * (row-major i*n+j) are read and written in place. Step-uniform tables: fold [T], the daily index of each step
+ * (filter::fold_to_daily_observation, kalman.h:114-116); w [n/2+1], the distinct values of W by folded distance
+ * min(|i-j|, n-|i-j|) (state::make_covariance, kalman.h:37-50); v2 = std_error_bias_measurements^2.
+ * mode 0, filter (filter::update): a non-finite bias still does P += W and leaves x and k untouched.
+ * mode 1, predictor (bias_predictor::update_with_forecast / compute_running_bias, kalman.h:173-185, 203-236): a
+ * non-finite bias skips the step, the state stays bitwise unchanged.
+ * out [T][M], or NULL: the running bias of compute_running_bias (mode 1 only). Every save_every steps from step 0
+ * the profile is a snapshot of x; out[t] is written before step t's update as the average of that snapshot over
+ * the pieces piece_begin[t] .. piece_begin[t+1] of step t (CSR; piece_ix the profile index, piece_seconds the
+ * length of each piece): pieces in order, sum of v * seconds over the finite v, one division by the sum of their
+ * seconds (accumulate_value as profile_accessor::value(i) calls it, core/time_series.h:203-305, 682-688).
+ * M == 0 or T == 0 returns 0 and writes nothing; n outside 1..32 is an error. Every element of the update is
+ * evaluated as written (no FMA, every division a division), so the result is bit-identical to
+ * shyft_hip_kalman_run_host. */
+int shyft_hip_kalman_run(int device, int n, size_t M, size_t T, const double* bias, const int32_t* fold, const double* w,
+                         double v2, int mode, double* x, double* k, double* P, double* out, int save_every,
+                         const int32_t* piece_begin, const int32_t* piece_ix, const double* piece_seconds);
+/* The same arithmetic in plain C++, no device call (core/kalman.h:127-145, 173-185, 203-236); any n >= 1. */
+int shyft_hip_kalman_run_host(int n, size_t M, size_t T, const double* bias, const int32_t* fold, const double* w, double v2,
+                              int mode, double* x, double* k, double* P, double* out, int save_every,
+                              const int32_t* piece_begin, const int32_t* piece_ix, const double* piece_seconds);
+/* state::state's matrices (core/kalman.h:31-50): P = make_covariance(n, covariance_init, hourly_correlation) and
+ * W = make_covariance(n, process_noise_init^2, hourly_correlation), both [n][n], with detmath::pow for the power so
+ * the matrices are the same on every machine. */
+int shyft_hip_kalman_initial_state(int n, double covariance_init, double hourly_correlation, double process_noise_init,
+                                   double* P, double* W);
+/* HIP-event milliseconds of the kernel of the last shyft_hip_kalman_run on this device (device < 0 = current), copies
+ * excluded. (No reference counterpart in core/kalman.h: measurement only.) */
+double shyft_hip_kalman_last_ms(int device);
+
 size_t shyft_hip_number_of_catchments(const shyft_hip_region* h);
 int shyft_hip_catchment_ids(const shyft_hip_region* h, int64_t* cids);
 

@@ -22,6 +22,7 @@ from ._api import (  # noqa: F401  (re-exported names)
     POINT_INSTANT_VALUE, POINT_AVERAGE_VALUE, IDWParameter, IDWTemperatureParameter, IDWPrecipitationParameter,
     InterpolationParameter, UHGParameter, River, RiverNetwork, make_uhg_from_gamma, average_values, FlowAdjustResult,
     find_min_single_variable, BTKParameter, OKCovarianceType, OKParameter, GAUSSIAN, EXPONENTIAL,
+    KalmanParameter, KalmanState, KalmanFilter,
 )
 from . import _api
 
@@ -364,6 +365,133 @@ def ordinary_kriging(src, dst, time_axis, parameter):
     for d, gp in enumerate(dst):
         out.append(GeoPointSource(gp, TimeSeries(time_axis, values[:, d], POINT_AVERAGE_VALUE)))
     return out
+
+
+# ---- Kalman bias prediction (core/kalman.h; api/boostpython/api_kalman.cpp) -------------------------------------------
+def _series_of(v):
+    """the _PointTs of every item of a source vector or a TsVector"""
+    return [(x.ts if hasattr(x, "ts") else x)._ts for x in v]
+
+
+class KalmanBiasPredictor(_api._KalmanBiasPredictor):
+    """api.KalmanBiasPredictor (api_kalman.cpp:134-204; kalman::bias_predictor, core/kalman.h:154-238): learns the
+    daily bias pattern of a forecast against observations with a KalmanFilter. `.filter`, `.state`; a single
+    predictor runs on the host path of the batched filter and needs no device."""
+
+    def update_with_forecast(self, fc_set, obs_ts, time_axis):
+        """feed a set of forecasts (TemperatureSourceVector or TsVector, oldest first) and the observations on the
+        steps of time_axis; afterwards .state.x is the estimated bias pattern"""
+        self._update_with_forecast(_series_of(fc_set), obs_ts._ts, time_axis)
+
+    def compute_running_bias(self, fc_ts, obs_ts, time_axis):
+        """the running bias series of one merged forecast against the observations: before each day, the bias
+        pattern learned so far is copied out (TimeSeries on time_axis, POINT_AVERAGE_VALUE)"""
+        return TimeSeries(time_axis, self._compute_running_bias(fc_ts._ts, obs_ts._ts, time_axis), POINT_AVERAGE_VALUE)
+
+    @staticmethod
+    def update_with_geo_forecast(bias_predictor, temperature_sources, observation_ts, time_axis):
+        bias_predictor.update_with_forecast(temperature_sources, observation_ts, time_axis)
+
+    @staticmethod
+    def update_with_forecast_vector(bias_predictor, temperature_sources, observation_ts, time_axis):
+        bias_predictor.update_with_forecast(temperature_sources, observation_ts, time_axis)
+
+    @staticmethod
+    def compute_running_bias_ts(bias_predictor, forecast_ts, observation_ts, time_axis):
+        return bias_predictor.compute_running_bias(forecast_ts, observation_ts, time_axis)
+
+
+class KalmanBiasPredictorVector:
+    """One KalmanBiasPredictor per point, all sharing the filter, updated in one device call (no reference
+    counterpart: the per-point loop of the reference's grid post-processing, shyft/tests/api/test_grid_pp.py:46-58,
+    over the points of a grid). Point j is bitwise what a single KalmanBiasPredictor gives on the series of point j.
+    host=True on either method runs the host restatement of the kernel."""
+
+    def __init__(self, filter, n_points):
+        self.filter = KalmanFilter(KalmanParameter(filter.parameter))
+        self.n_points = int(n_points)
+        if self.n_points < 0:
+            raise RuntimeError("KalmanBiasPredictorVector: n_points must not be negative")
+        s0 = self.filter.create_initial_state()
+        n = s0.size()
+        self._w = np.array(s0.W)[0, :n // 2 + 1].copy() if n else np.empty(0)
+        self._W = np.array(s0.W)
+        self._x = np.zeros((n, self.n_points))
+        self._k = np.zeros((n, self.n_points))
+        self._P = np.repeat(np.array(s0.P).reshape(n * n, 1), self.n_points, axis=1)
+
+    def __len__(self):
+        return self.n_points
+
+    def size(self):
+        return self.n_points
+
+    @property
+    def x(self):
+        return self._x.T.copy()
+
+    @property
+    def k(self):
+        return self._k.T.copy()
+
+    @property
+    def P(self):
+        n = self._x.shape[0]
+        return self._P.T.reshape(self.n_points, n, n).copy()
+
+    def __getitem__(self, j):
+        if not -self.n_points <= j < self.n_points:
+            raise IndexError(j)
+        s = self.filter.create_initial_state()
+        s._set(self._x[:, j].tolist(), self._k[:, j].tolist(), self._P[:, j].tolist())
+        return KalmanBiasPredictor(self.filter, s)
+
+    def _check_set(self, v, what):
+        if len(v) != self.n_points:
+            raise RuntimeError(f"KalmanBiasPredictorVector: {what} holds {len(v)} series, the vector has "
+                               f"{self.n_points} points")
+        return _series_of(v)
+
+    def _run(self, bias, tables, n_cycles, running, host):
+        from ..region import kalman_run, KALMAN_PREDICTOR
+        fold = np.tile(tables["fold"], n_cycles)
+        self._x, self._k, P, out = kalman_run(bias, fold, self._w, tables["v2"], self._x, self._k, self._P,
+                                              mode=KALMAN_PREDICTOR, running=running, host=host)
+        self._P = P.reshape(self._P.shape)
+        return out
+
+    def update_with_forecast(self, fc_sets, obs_set, time_axis, host=False):
+        """fc_sets: a list of forecast cycles, oldest first; each cycle and obs_set hold n_points series (source
+        vectors or TsVector), and the series of one cycle share one time axis. Per point the update sequence is the
+        reference's (kalman.h:173-185): cycles outer, steps of time_axis inner."""
+        obs = self._check_set(obs_set, "obs_set")
+        cycles = []
+        for c, fc_set in enumerate(fc_sets):
+            fc = self._check_set(fc_set, f"forecast cycle {c}")
+            if not _api._kalman_same_axis(fc):
+                raise RuntimeError(f"KalmanBiasPredictorVector: the series of forecast cycle {c} differ in time axis")
+            cycles.append(fc)
+        if not cycles or not self.n_points or not time_axis.size():
+            return
+        obs_avg = _api._kalman_average_set(obs, time_axis)  # every observation averaged once, for all cycles
+        bias = np.concatenate([_api._kalman_observed_bias_set(fc, obs_avg, time_axis) for fc in cycles], axis=0)
+        self._run(bias, self.filter._tables(time_axis), len(cycles), None, host)
+
+    def compute_running_bias(self, fc_set, obs_set, time_axis, host=False):
+        """the running bias of every point (kalman.h:203-236): a vector of the input's type, one series per point"""
+        obs = self._check_set(obs_set, "obs_set")
+        fc = self._check_set(fc_set, "fc_set")
+        t = self.filter._tables(time_axis, True)
+        out = np.empty((time_axis.size(), self.n_points))
+        if self.n_points and time_axis.size():
+            bias = _api._kalman_observed_bias_set(fc, _api._kalman_average_set(obs, time_axis), time_axis)
+            out = self._run(bias, t, 1,
+                            (t["save_every"], t["piece_begin"], t["piece_ix"], t["piece_seconds"]), host)
+        r = type(fc_set)()
+        for j, src in enumerate(fc_set):
+            ts = TimeSeries(time_axis, out[:, j], POINT_AVERAGE_VALUE)
+            r.append(type(src)(src.mid_point(), ts) if hasattr(src, "ts") else ts)
+        return r
 
 
 class ARegionEnvironment:

@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "calibration.hpp"
+#include "kalman.hpp"
 #include "region_model.hpp"
 
 namespace py = pybind11;
@@ -415,6 +416,125 @@ PYBIND11_MODULE(_api, m) {
         }
         return py::array_t<double>({T, D}, out.data());
     });
+    // KalmanParameter, KalmanState, KalmanFilter, KalmanBiasPredictor (api/boostpython/api_kalman.cpp:22-204 over
+    // core/kalman.h); the single-filter objects run on the host path of the batched entry (shyft_hip_kalman_run_host)
+    {
+        namespace kf = shyft_hip::host::kalman;
+        auto vec = [](const std::vector<double>& v) { return py::array_t<double>(v.size(), v.data()); };
+        auto mat = [](const std::vector<double>& v, int n) {
+            return py::array_t<double>({py::ssize_t(n), py::ssize_t(n)}, v.data());
+        };
+        py::class_<kf::parameter>(m, "KalmanParameter",
+                                  "Defines the parameters that tune the kalman-filter algorithm for temperature type of signals")
+            .def(py::init<int, double, double, double, double>(), py::arg("n_daily_observations") = 8,
+                 py::arg("hourly_correlation") = 0.93, py::arg("covariance_init") = 0.5,
+                 py::arg("std_error_bias_measurements") = 2.0, py::arg("ratio_std_w_over_v") = 0.15)
+            .def(py::init<const kf::parameter&>(), py::arg("const_ref"))
+            .def_readwrite("n_daily_observations", &kf::parameter::n_daily_observations)
+            .def_readwrite("hourly_correlation", &kf::parameter::hourly_correlation)
+            .def_readwrite("covariance_init", &kf::parameter::covariance_init)
+            .def_readwrite("std_error_bias_measurements", &kf::parameter::std_error_bias_measurements)
+            .def_readwrite("ratio_std_w_over_v", &kf::parameter::ratio_std_w_over_v);
+        py::class_<kf::state>(m, "KalmanState",
+                              "The state of the kalman bias filter: x [n] best estimate, k [n] gain, P [n x n] covariance, "
+                              "W [n x n] process noise")
+            .def(py::init<>())
+            .def(py::init<int, double, double, double>(), py::arg("n_daily_observations"), py::arg("covariance_init"),
+                 py::arg("hourly_correlation"), py::arg("process_noise_init"))
+            .def(py::init<const kf::state&>(), py::arg("clone"))
+            .def("size", &kf::state::size)
+            .def_static("get_x", [](const kf::state& s) { return s.x; }, py::arg("state"))
+            .def_static("get_k", [](const kf::state& s) { return s.k; }, py::arg("state"))
+            .def_static("get_P", [](const kf::state& s) { return s.P; }, py::arg("state"))
+            .def_static("get_W", [](const kf::state& s) { return s.W; }, py::arg("state"))
+            .def_property_readonly("x", [vec](const kf::state& s) { return vec(s.x); })
+            .def_property_readonly("k", [vec](const kf::state& s) { return vec(s.k); })
+            .def_property_readonly("P", [mat](const kf::state& s) { return mat(s.P, s.size()); })
+            .def_property_readonly("W", [mat](const kf::state& s) { return mat(s.W, s.size()); })
+            .def("_set", [](kf::state& s, const std::vector<double>& x, const std::vector<double>& k,
+                            const std::vector<double>& P) {
+                if (x.size() != s.x.size() || k.size() != s.k.size() || P.size() != s.P.size())
+                    throw std::runtime_error("kalman: state size mismatch");
+                s.x = x;
+                s.k = k;
+                s.P = P;
+            })
+            .def("__deepcopy__", [](const kf::state& s, py::dict) { return kf::state(s); });
+        py::class_<kf::filter>(m, "KalmanFilter",
+                               "Specialized kalman filter for temperature (solar-driven daily bias patterns)")
+            .def(py::init<>())
+            .def(py::init<const kf::parameter&>(), py::arg("p"))
+            .def("create_initial_state", &kf::filter::create_initial_state)
+            .def("update", [](const kf::filter& f, double observed_bias, double t, kf::state& s) {
+                     f.update(observed_bias, to_us(t), s);
+                 }, py::arg("observed_bias"), py::arg("t"), py::arg("state"))
+            .def("_fold_to_daily_observation", [](const kf::filter& f, double t) {
+                     return f.fold_to_daily_observation(to_us(t));
+                 }, py::arg("t"))
+            .def("_tables", [](const kf::filter& f, const fixed_dt& ta, bool running) {
+                     py::dict d;
+                     const auto fold = f.fold_table(ta);
+                     d["fold"] = py::array_t<int32_t>(fold.size(), fold.data());
+                     d["v2"] = f.v2();
+                     if (running) {
+                         const auto r = f.running(ta);
+                         d["save_every"] = r.save_every;
+                         d["piece_begin"] = py::array_t<int32_t>(r.piece_begin.size(), r.piece_begin.data());
+                         d["piece_ix"] = py::array_t<int32_t>(r.piece_ix.size(), r.piece_ix.data());
+                         d["piece_seconds"] = py::array_t<double>(r.piece_seconds.size(), r.piece_seconds.data());
+                     }
+                     return d;
+                 }, py::arg("time_axis"), py::arg("running") = false)
+            .def_readwrite("parameter", &kf::filter::p);
+        py::class_<kf::bias_predictor>(m, "_KalmanBiasPredictor")
+            .def(py::init<>())
+            .def(py::init<const kf::filter&>(), py::arg("filter"))
+            .def(py::init<const kf::filter&, const kf::state&>(), py::arg("filter"), py::arg("state"))
+            .def("_update_with_forecast", &kf::bias_predictor::update_with_forecast)
+            .def("_compute_running_bias", [](kf::bias_predictor& bp, const point_ts& fc, const point_ts& obs,
+                                             const fixed_dt& ta) {
+                auto v = bp.compute_running_bias(fc, obs, ta);
+                return py::array_t<double>(v.size(), v.data());
+            })
+            .def_readonly("filter", &kf::bias_predictor::f)
+            .def_readwrite("state", &kf::bias_predictor::s);
+        // the host preparation of KalmanBiasPredictorVector, one call per set instead of one per point:
+        // the averages of a set of series on ta, [T][M], and fc - obs of a forecast cycle against them
+        m.def("_kalman_average_set", [](const py::list& set, const fixed_dt& ta) {
+            const size_t T = ta.size(), M = set.size();
+            py::array_t<double> out({py::ssize_t(T), py::ssize_t(M)});
+            double* o = out.mutable_data();
+            for (size_t j = 0; j < M; ++j) {
+                const auto v = average_values(set[j].cast<const point_ts&>(), ta);
+                for (size_t i = 0; i < T; ++i) o[i * M + j] = v[i];
+            }
+            return out;
+        });
+        m.def("_kalman_observed_bias_set", [](const py::list& fc, const py::array_t<double, py::array::c_style>& obs_avg,
+                                              const fixed_dt& ta) {
+            const size_t T = ta.size(), M = fc.size();
+            if (obs_avg.ndim() != 2 || size_t(obs_avg.shape(0)) != T || size_t(obs_avg.shape(1)) != M)
+                throw std::runtime_error("kalman: the observation averages do not match the forecast set");
+            py::array_t<double> out({py::ssize_t(T), py::ssize_t(M)});
+            double* o = out.mutable_data();
+            const double* a = obs_avg.data();
+            std::vector<double> col(T);
+            for (size_t j = 0; j < M; ++j) {
+                for (size_t i = 0; i < T; ++i) col[i] = a[i * M + j];
+                const auto v = kf::observed_bias(fc[j].cast<const point_ts&>(), col, ta);
+                for (size_t i = 0; i < T; ++i) o[i * M + j] = v[i];
+            }
+            return out;
+        });
+        // true when every series of the set has the time axis of the first
+        m.def("_kalman_same_axis", [](const py::list& set) {
+            for (size_t j = 1; j < set.size(); ++j) {
+                const point_ts &a = set[0].cast<const point_ts&>(), &b = set[j].cast<const point_ts&>();
+                if (a.t != b.t || a.t_end != b.t_end) return false;
+            }
+            return true;
+        });
+    }
     py::class_<interpolation_parameter>(m, "InterpolationParameter")
         .def(py::init<>())
         .def(py::init([](const btk_parameter& t, const idw_precipitation_parameter& p, const idw_parameter& ws,

@@ -440,3 +440,61 @@ def ordinary_kriging(src_xyz, src_values, ok_param, dst_xyz, device: int = -1, h
         check(L.shyft_hip_ordinary_kriging(device, xyz.shape[0], _ptr(xyz), _ptr(v), v.shape[0], _ptr(p), d.shape[0],
                                            _ptr(d), _ptr(out)), None)
     return out
+
+
+KALMAN_FILTER, KALMAN_PREDICTOR = 0, 1
+
+
+def kalman_initial_state(n: int, covariance_init: float, hourly_correlation: float, process_noise_init: float):
+    """state::state's matrices (shyft_hip_kalman_initial_state; core/kalman.h:31-50): (P, W), both [n][n]."""
+    n = int(n)
+    P, W = np.empty((n, n)), np.empty((n, n))
+    check(lib().shyft_hip_kalman_initial_state(n, float(covariance_init), float(hourly_correlation),
+                                               float(process_noise_init), _ptr(P), _ptr(W)), None)
+    return P, W
+
+
+def kalman_run(bias, fold, w, v2, x, k, P, mode: int = KALMAN_PREDICTOR, running=None, device: int = -1,
+               host: bool = False):
+    """M independent Kalman bias filters over T steps in one call (shyft_hip_kalman_run; core/kalman.h:127-236).
+    bias [T][M]; fold [T] the daily index of each step; w [n/2+1] the values of W by folded distance; v2 the squared
+    measurement error; x [n][M], k [n][M], P [n*n][M] (or [n][n][M]) the start state. mode KALMAN_FILTER: a non-finite
+    bias still grows P; KALMAN_PREDICTOR: it skips the step. running = (save_every, piece_begin [T+1], piece_ix,
+    piece_seconds) also gives the running bias [T][M] (predictor mode). host=True evaluates the same arithmetic on
+    the host (shyft_hip_kalman_run_host), which the device result is bit-identical to. Returns (x, k, P, out) as new
+    arrays, P shaped [n][n][M], out None without `running`."""
+    L = lib()
+    x = np.array(x, dtype=np.float64, order="C", ndmin=2)
+    n, M = x.shape
+    k = np.array(k, dtype=np.float64, order="C").reshape(n, M)
+    P = np.array(P, dtype=np.float64, order="C").reshape(n * n, M)
+    b = np.ascontiguousarray(bias, dtype=np.float64).reshape(-1, M) if M else np.empty((len(fold), 0))
+    T = b.shape[0]
+    f = np.ascontiguousarray(fold, dtype=np.int32).reshape(-1)
+    ww = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    if f.shape[0] != T:
+        raise ValueError("kalman_run: fold and bias differ in the number of steps")
+    if ww.shape[0] != n // 2 + 1:
+        raise ValueError("kalman_run: w must have n/2+1 values")
+    out, save_every, pb, pi, ps = None, 1, None, None, None
+    if running is not None:
+        save_every = int(running[0])
+        pb = np.ascontiguousarray(running[1], dtype=np.int32).reshape(-1)
+        pi = np.ascontiguousarray(running[2], dtype=np.int32).reshape(-1)
+        ps = np.ascontiguousarray(running[3], dtype=np.float64).reshape(-1)
+        if pb.shape[0] != T + 1 or pi.shape[0] != ps.shape[0] or (T and pb[-1] != pi.shape[0]):
+            raise ValueError("kalman_run: the piece table does not match the steps")
+        out = np.empty((T, M))
+    tail = (float(v2), int(mode), _ptr(x), _ptr(k), _ptr(P), _ptr(out) if out is not None else None, save_every,
+            _ptr(pb) if pb is not None else None, _ptr(pi) if pi is not None else None,
+            _ptr(ps) if ps is not None else None)
+    if host:
+        check(L.shyft_hip_kalman_run_host(n, M, T, _ptr(b), _ptr(f), _ptr(ww), *tail), None)
+    else:
+        check(L.shyft_hip_kalman_run(device, n, M, T, _ptr(b), _ptr(f), _ptr(ww), *tail), None)
+    return x, k, P.reshape(n, n, M), out
+
+
+def kalman_last_ms(device: int = -1) -> float:
+    """HIP-event milliseconds of the last kalman_run kernel on the device, copies excluded."""
+    return float(lib().shyft_hip_kalman_last_ms(device))
