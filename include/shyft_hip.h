@@ -365,6 +365,45 @@ int shyft_hip_kalman_initial_state(int n, double covariance_init, double hourly_
  * excluded. (No reference counterpart in core/kalman.h: measurement only.) */
 double shyft_hip_kalman_last_ms(int device);
 
+/* Quantile mapping of weighted forecasts onto historical scenarios (core/time_series_qm.h): per step, quantile_index
+ * (:34-52) of the F forecast and the P scenario values, wvo_accessor's normalised weights (:187-210),
+ * compute_weighted_quantiles (:80-100) or compute_interp_weighted_quantiles (:139-170) with one quantile per finite
+ * scenario, and quantile_mapping's write-back by scenario rank with the interpolation blend (:325-347), in one launch
+ * of kernels/qm.hip on a device (device < 0 = current). Host pointers, stateless. B independent problems share the
+ * axis, the weights and the shapes: fc [B][T][F] and pri [B][T][P] are the values averaged onto the axis (NaN = not
+ * covered), w [F] the weight of each forecast, out [B][T][P]. mode [T] and interp_weight [T] are what
+ * quantile_mapping derives from the times (:310-311, :328, :335-339): PRIOR, the step keeps its scenarios; QM, scenario
+ * of rank i gets quantile i; QM_BLEND, (1 - interp_weight) * quantile + interp_weight * scenario. A step without a
+ * finite forecast is PRIOR; scenarios that are not finite at a QM step get NaN. Equal values are ranked by ascending
+ * series index (the reference's std::sort leaves their order open; +0.0 and -0.0 are equal). With one finite scenario
+ * the quantile is the lowest forecast for both kinds (the reference reads out of range for the interpolated kind).
+ * Every weight must be finite and > 0: the reference's loops do not terminate otherwise. B*T == 0 or P == 0 returns 0
+ * and launches nothing; F or P above SHYFT_HIP_QM_MAX_SERIES is an error on the device. The prefix sums are formed
+ * sequentially in rank order and every operation is evaluated as written (no FMA), so the result is bit-identical to
+ * shyft_hip_quantile_map_host. */
+#define SHYFT_HIP_QM_MAX_SERIES 1024
+#define SHYFT_HIP_QM_PRIOR 0
+#define SHYFT_HIP_QM_QM 1
+#define SHYFT_HIP_QM_BLEND 2
+int shyft_hip_quantile_map(int device, size_t B, size_t T, size_t F, size_t P, const double* fc, const double* w,
+                           const double* pri, const int32_t* mode, const double* interp_weight,
+                           int interpolated_quantiles, double* out);
+/* The same arithmetic in plain C++ (host/qm.hpp map_step; core/time_series_qm.h:34-210, 325-347), no device call; any
+ * F and P. */
+int shyft_hip_quantile_map_host(size_t B, size_t T, size_t F, size_t P, const double* fc, const double* w,
+                                const double* pri, const int32_t* mode, const double* interp_weight,
+                                int interpolated_quantiles, double* out);
+/* The launch shape of the last shyft_hip_quantile_map kernel on this device (device < 0 = current): WAVE, one
+ * wavefront per (problem, step) when the padded max(F, P) is at most 64; GROUP, one workgroup each. (No reference
+ * counterpart in core/time_series_qm.h: test and measurement aid.) */
+#define SHYFT_HIP_QM_PATH_NONE 0
+#define SHYFT_HIP_QM_PATH_WAVE 1
+#define SHYFT_HIP_QM_PATH_GROUP 2
+int shyft_hip_quantile_map_last_path(int device);
+/* HIP-event milliseconds of the last shyft_hip_quantile_map kernel on this device, copies excluded. (No reference
+ * counterpart in core/time_series_qm.h: measurement only.) */
+double shyft_hip_quantile_map_last_ms(int device);
+
 size_t shyft_hip_number_of_catchments(const shyft_hip_region* h);
 int shyft_hip_catchment_ids(const shyft_hip_region* h, int64_t* cids);
 

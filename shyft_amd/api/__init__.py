@@ -22,7 +22,7 @@ from ._api import (  # noqa: F401  (re-exported names)
     POINT_INSTANT_VALUE, POINT_AVERAGE_VALUE, IDWParameter, IDWTemperatureParameter, IDWPrecipitationParameter,
     InterpolationParameter, UHGParameter, River, RiverNetwork, make_uhg_from_gamma, average_values, FlowAdjustResult,
     find_min_single_variable, BTKParameter, OKCovarianceType, OKParameter, GAUSSIAN, EXPONENTIAL,
-    KalmanParameter, KalmanState, KalmanFilter,
+    KalmanParameter, KalmanState, KalmanFilter, no_utctime,
 )
 from . import _api
 
@@ -260,6 +260,66 @@ class TsFactory:
 
     def create_point_ts(self, n, tstart, dt, values, interpretation=POINT_INSTANT_VALUE):
         return TimeSeries(TimeAxisFixedDeltaT(tstart, dt, n), values, interpretation)
+
+
+class TsVectorSet(_Vector):
+    """api.TsVectorSet: a vector of TsVector, the forecast sets of quantile_map_forecast (api_time_series.cpp:408-417)."""
+
+    def __init__(self, clone_me=()):
+        super().__init__(TsVector(tsv) for tsv in clone_me)
+
+
+# ---- quantile mapping (core/time_series_qm.h; time_series_dd.cpp:1167-1200; api_time_series.cpp:24-31, 418-443) -------
+def quantile_map_forecast(forecast_sets, set_weights, historical_data, time_axis, interpolation_start,
+                          interpolation_end=no_utctime, interpolated_quantiles=False, *, host=False):
+    """Computes the quantile-mapped forecast from the supplied input (api.quantile_map_forecast, the reference's 5-, 6-
+    and 7-argument forms).
+
+    forecast_sets: TsVectorSet, each a TsVector of forecasts (they may differ in size and length); set_weights: one
+    weight per set, every one finite and > 0 (the reference's quantile walk does not terminate otherwise, so they are
+    refused here); historical_data: TsVector of scenarios that should cover time_axis; interpolation_start /
+    interpolation_end: the period (seconds since epoch, no_utctime for none) over which the result goes linearly
+    from the mapped forecast to the scenario, the end defaulting to the end of the forecasts; interpolated_quantiles:
+    interpolate between the forecast quantiles instead of taking the one at or below. Returns a TsVector of
+    POINT_AVERAGE_VALUE series on time_axis: quantile mapped up to the end of the interpolation period (or of the
+    forecasts), the scenarios' own averages after it. Values that are equal at a step are ranked by series index.
+
+    Every series is averaged onto the mapped part of the axis once; the mapping of all steps is one call of
+    region.quantile_map on the device, or on the host (same arithmetic, bit-identical) with host=True or when there
+    are more than region.QM_MAX_SERIES forecasts or scenarios."""
+    from ..region import quantile_map, QM_MAX_SERIES
+    if len(forecast_sets) < 1:  # time_series_dd.cpp:1176-1197
+        raise RuntimeError("forecast_set must contain at least one forecast")
+    if len(historical_data) < 2:
+        raise RuntimeError("historical_data should have more than one time-series")
+    if len(forecast_sets) != len(set_weights):
+        raise RuntimeError(f"The size of weights ({len(set_weights)}), must match number of forecast-sets "
+                           f"({len(forecast_sets)})")
+    if time_axis.size() == 0:
+        raise RuntimeError("time-axis should have at least one step")
+    p0, p1 = time_axis.total_period()
+    if interpolation_start != no_utctime:
+        if not p0 <= interpolation_start < p1:
+            raise RuntimeError(f"interpolation_start {interpolation_start} is not within time_axis period [{p0}, {p1})")
+        if interpolation_end != no_utctime and not p0 <= interpolation_end < p1:
+            raise RuntimeError(f"interpolation_end {interpolation_end} is not within time_axis period [{p0}, {p1})")
+    if not all(np.isfinite(w) and w > 0 for w in set_weights):
+        raise RuntimeError("quantile_map_forecast: every set weight must be finite and > 0")
+    forecasts, weights = [], []  # time_series_qm.h:406-415
+    for tsv, w in zip(forecast_sets, set_weights):
+        forecasts.extend(_series_of(tsv))
+        weights.extend([float(w)] * len(tsv))
+    historical = _series_of(historical_data)
+    n_qm, fc, pri, mode, interp_weight = _api._qm_plan(forecasts, historical, time_axis, float(interpolation_start),
+                                                       float(interpolation_end))
+    on_host = host or fc.shape[1] > QM_MAX_SERIES or pri.shape[1] > QM_MAX_SERIES
+    qm = quantile_map(fc, weights, pri, mode, interp_weight, interpolated=interpolated_quantiles, host=on_host)
+    if n_qm < time_axis.size():  # merge_qm_result (:363-374)
+        qm = np.concatenate([qm, _api._qm_tail(historical, time_axis, n_qm).T], axis=0)
+    out = TsVector()
+    for k in range(len(historical)):
+        out.append(TimeSeries(time_axis, qm[:, k], POINT_AVERAGE_VALUE))
+    return out
 
 
 # ---- geo-located sources and the region environment (api/api.h:78-168) -----------------------------------------------

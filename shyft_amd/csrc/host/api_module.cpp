@@ -18,6 +18,7 @@
 
 #include "calibration.hpp"
 #include "kalman.hpp"
+#include "qm.hpp"
 #include "region_model.hpp"
 
 namespace py = pybind11;
@@ -533,6 +534,55 @@ PYBIND11_MODULE(_api, m) {
                 if (a.t != b.t || a.t_end != b.t_end) return false;
             }
             return true;
+        });
+    }
+    // The host work of quantile_map_forecast (core/time_series_qm.h:401-450; host/qm.hpp): the qm axis, every series
+    // averaged onto it once as dense [T][F] / [T][P] matrices (NaN = not covered), the per-step modes, and the
+    // historical tail. The mapping itself is region.quantile_map.
+    {
+        namespace qm = shyft_hip::host::qm;
+        static const double no_utctime_s = double(qm::no_utctime) / 1e6;
+        m.attr("no_utctime") = no_utctime_s;
+        auto qm_us = [](double s) { return s > no_utctime_s ? to_us(s) : qm::no_utctime; };
+        m.def("_qm_plan", [qm_us](const py::list& forecasts, const py::list& historical, const fixed_dt& ta,
+                                  double interpolation_start, double interpolation_end) {
+            std::vector<const point_ts*> fc;
+            for (auto h : forecasts) fc.push_back(&h.cast<const point_ts&>());
+            const utctime i_start = qm_us(interpolation_start), i_end = qm_us(interpolation_end);
+            const qm::plan_t pl = qm::plan(fc, ta, i_start, i_end);
+            const size_t T = pl.qm_n_steps, F = fc.size(), P = historical.size();
+            py::array_t<double> fcm({py::ssize_t(T), py::ssize_t(F)}), prim({py::ssize_t(T), py::ssize_t(P)});
+            double* o = fcm.mutable_data();
+            for (size_t j = 0; j < F; ++j) {
+                const auto v = average_values(*fc[j], pl.qm_time_axis);
+                for (size_t i = 0; i < T; ++i) o[i * F + j] = v[i];
+            }
+            o = prim.mutable_data();
+            for (size_t j = 0; j < P; ++j) {
+                const auto v = average_values(historical[j].cast<const point_ts&>(), pl.qm_time_axis);
+                for (size_t i = 0; i < T; ++i) o[i * P + j] = v[i];
+            }
+            std::vector<int32_t> mode;
+            std::vector<double> iw;
+            qm::step_modes(pl.qm_time_axis, pl.fc_period, i_start, i_end, mode, iw);
+            return py::make_tuple(T, fcm, prim, py::array_t<int32_t>(mode.size(), mode.data()),
+                                  py::array_t<double>(iw.size(), iw.data()));
+        });
+        m.def("_qm_tail", [](const py::list& historical, const fixed_dt& ta, size_t qm_n_steps) {
+            if (qm_n_steps > ta.size()) throw std::runtime_error("quantile_map_forecast: qm axis longer than the time axis");
+            const size_t n = ta.size() - qm_n_steps, P = historical.size();
+            py::array_t<double> out({py::ssize_t(P), py::ssize_t(n)});
+            double* o = out.mutable_data();
+            for (size_t j = 0; j < P; ++j) {
+                const auto v = qm::historical_tail(historical[j].cast<const point_ts&>(), ta, qm_n_steps);
+                std::copy(v.begin(), v.end(), o + j * n);
+            }
+            return out;
+        });
+        // accumulate_stair_case / accumulate_linear (core/time_series_average.h:105-275) by the series' point type
+        m.def("_accumulate", [](const point_ts& ts, const fixed_dt& ta, bool avg) {
+            const auto v = ts.fx == POINT_AVERAGE_VALUE ? accumulate_stair_case(ta, ts, avg) : accumulate_linear(ta, ts, avg);
+            return py::array_t<double>(v.size(), v.data());
         });
     }
     py::class_<interpolation_parameter>(m, "InterpolationParameter")

@@ -8,6 +8,9 @@
 // average_accessor step that resamples a source onto the model time axis before
 // interpolation (region_model.h:135-145 -> time_series.h:2033-2072 ->
 // accumulate_value/average_value time_series.h:202-310).
+// accumulate_linear / accumulate_stair_case are the non-NaN integral or average
+// over a time axis (core/time_series_average.h:105-275) that quantile mapping
+// uses for its historical tail (host/qm.hpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -206,6 +209,163 @@ inline std::vector<double> average_values(const point_ts& source, const fixed_dt
     for (size_t i = 0; i < ta.size(); ++i) {
         if (ta.time(i) >= src_end) r[i] = std::numeric_limits<double>::quiet_NaN();
         else r[i] = average_value(source, ta.period(i), last_idx, linear);
+    }
+    return r;
+}
+
+// point_ts<TA>::index_of (time_series.h:343; time_axis.h:100-106, 317-327): the interval that holds tx, npos outside
+// the series' total period.
+inline size_t index_of(const point_ts& ts, utctime tx) {
+    if (ts.t.empty() || tx < ts.t.front() || tx >= ts.t_end) return npos;
+    return size_t(std::upper_bound(ts.t.begin(), ts.t.end(), tx) - ts.t.begin()) - 1;
+}
+
+// accumulate_linear (core/time_series_average.h:105-193), statement by statement: the non-NaN integral (seconds) or
+// true average of a linear-between-points series over every interval of ta. Time is counted in ticks
+// (microseconds, :26-27); a value needs a finite point at both ends of a piece (:55-78).
+inline std::vector<double> accumulate_linear(const fixed_dt& ta, const point_ts& ts, bool avg) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> r(ta.size(), nan);
+    if (ta.size() == 0 || ts.size() < 2 || ts.time(0) >= ta.total_period().end ||
+        ts.time(ts.size() - 1) <= ta.total_period().start)
+        return r;
+    auto a_seconds = [](double a) { return a / double(US); };
+    size_t s = index_of(ts, ta.period(0).start);
+    if (s == npos) s = 0;
+    utctime s_t0 = ts.t[s];
+    double s_v = ts.v[s];
+    bool s_finite = std::isfinite(s_v);
+    size_t e = 0;
+    utctime e_t0 = 0;
+    double e_v = 0.0;
+    bool e_finite = false;
+    const size_t n = ts.size();
+    double a = 0, b = 0;
+    for (size_t i = 0; i < ta.size(); ++i) {
+        double area = 0.0;
+        int64_t t_sum = 0;
+        const utcperiod p = ta.period(i);
+    search_s_finite:
+        while (!s_finite) {
+            ++s;
+            if (s + 1 >= n) {
+                if (t_sum) r[i] = avg ? area / t_sum : a_seconds(area);
+                return r;
+            }
+            s_t0 = ts.t[s];
+            s_v = ts.v[s];
+            s_finite = std::isfinite(s_v);
+        }
+        if (s_t0 >= p.end) {
+            if (t_sum) r[i] = avg ? area / t_sum : a_seconds(area);
+            continue;
+        }
+        if (e != s + 1) {
+        advance_e_point:
+            e = s + 1;
+            if (e == n) {
+                if (t_sum) r[i] = avg ? area / t_sum : a_seconds(area);
+                return r;
+            }
+            e_t0 = ts.t[e];
+            e_v = ts.v[e];
+            e_finite = std::isfinite(e_v);
+            if (e_finite) {
+                a = (e_v - s_v) / double(e_t0 - s_t0);
+                b = s_v - a * double(s_t0);
+            } else {
+                s = e;
+                s_finite = false;
+                goto search_s_finite;
+            }
+        }
+        {
+            const utctime s_t = std::max(s_t0, p.start);
+            const utctime e_t = std::min(e_t0, p.end);
+            const int64_t dt = e_t - s_t;
+            area += (0.5 * a * double(s_t + e_t) + b) * dt;
+            t_sum += dt;
+        }
+        if (e_t0 >= p.end) {
+            r[i] = avg ? area / t_sum : a_seconds(area);
+            continue;
+        }
+        s_t0 = e_t0;
+        s_v = e_v;
+        s = e;
+        goto advance_e_point;
+    }
+    return r;
+}
+
+// accumulate_stair_case (core/time_series_average.h:195-275), statement by statement: the same for a stair-case
+// series, whose last point extends to the end of its total period.
+inline std::vector<double> accumulate_stair_case(const fixed_dt& ta, const point_ts& ts, bool avg) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> r(ta.size(), nan);
+    if (ta.size() == 0 || ts.size() == 0 || ts.time(0) >= ta.total_period().end ||
+        ts.total_period().end <= ta.total_period().start)
+        return r;
+    auto a_seconds = [](double a) { return a / double(US); };
+    const utcperiod tp = ts.total_period();
+    size_t s = index_of(ts, ta.period(0).start);
+    if (s == npos) s = 0;
+    utctime s_t0 = ts.t[s];
+    double s_v = ts.v[s];
+    bool s_finite = std::isfinite(s_v);
+    utctime e_t0 = 0;
+    bool e_finite = false;
+    double e_v = 0.0;
+    const size_t n = ts.size();
+    for (size_t i = 0; i < ta.size(); ++i) {
+        double area = 0.0;
+        int64_t t_sum = 0;
+        const utcperiod p = ta.period(i);
+    search_s_finite:
+        while (!s_finite) {
+            ++s;
+            if (s >= n) {
+                if (t_sum) r[i] = avg ? area / t_sum : a_seconds(area);
+                return r;
+            }
+            s_t0 = ts.t[s];
+            s_v = ts.v[s];
+            s_finite = std::isfinite(s_v);
+        }
+        if (s_t0 >= p.end) {
+            if (t_sum) r[i] = avg ? area / t_sum : a_seconds(area);
+            continue;
+        }
+    find_partition_end:
+        if (s + 1 < n) {
+            e_t0 = ts.t[s + 1];
+            e_v = ts.v[s + 1];
+            e_finite = std::isfinite(e_v);
+        } else {
+            e_t0 = tp.end;
+            e_finite = false;
+        }
+        {
+            const utctime s_t = std::max(s_t0, p.start);
+            const utctime e_t = std::min(e_t0, p.end);
+            const int64_t dt = e_t - s_t;
+            area += s_v * dt;
+            t_sum += dt;
+        }
+        if (e_t0 <= p.end && s + 1 < n) {
+            s_t0 = e_t0;
+            s_v = e_v;
+            s_finite = e_finite;
+            ++s;
+            if (e_t0 == p.end) {
+                r[i] = avg ? area / t_sum : a_seconds(area);
+                continue;
+            }
+            if (s_finite) goto find_partition_end;
+            else goto search_s_finite;
+        }
+        r[i] = avg ? area / t_sum : a_seconds(area);
+        if (s + 1 >= n && p.end >= tp.end) return r;
     }
     return r;
 }

@@ -498,3 +498,51 @@ def kalman_run(bias, fold, w, v2, x, k, P, mode: int = KALMAN_PREDICTOR, running
 def kalman_last_ms(device: int = -1) -> float:
     """HIP-event milliseconds of the last kalman_run kernel on the device, copies excluded."""
     return float(lib().shyft_hip_kalman_last_ms(device))
+
+
+QM_PRIOR, QM_QM, QM_BLEND = 0, 1, 2
+QM_PATH_NONE, QM_PATH_WAVE, QM_PATH_GROUP = 0, 1, 2
+QM_MAX_SERIES = 1024
+
+
+def quantile_map(fc, w, pri, mode, interp_weight, interpolated: bool = False, device: int = -1,
+                 host: bool = False) -> np.ndarray:
+    """Quantile mapping of weighted forecasts onto scenarios, every (problem, step) in one call
+    (shyft_hip_quantile_map; core/time_series_qm.h:34-351). fc [B][T][F] and pri [B][T][P] (or [T][F] and [T][P] for
+    one problem) are the values averaged onto the axis, NaN where a series does not cover a step; w [F] the weight of
+    each forecast, finite and > 0; mode [T] QM_PRIOR / QM_QM / QM_BLEND and interp_weight [T] what quantile_mapping
+    derives from the times. interpolated selects compute_interp_weighted_quantiles. Equal values rank by ascending
+    series index. host=True evaluates the same arithmetic on the host (shyft_hip_quantile_map_host), which the device
+    result is bit-identical to, for any F and P; the device takes at most QM_MAX_SERIES of each. Returns out, shaped
+    like pri."""
+    L = lib()
+    p = np.ascontiguousarray(pri, dtype=np.float64)
+    f = np.ascontiguousarray(fc, dtype=np.float64)
+    if p.ndim not in (2, 3) or f.ndim != p.ndim or f.shape[:-1] != p.shape[:-1]:
+        raise ValueError("quantile_map: fc and pri must be [B][T][F] and [B][T][P], or [T][F] and [T][P]")
+    B = p.shape[0] if p.ndim == 3 else 1
+    T, P, F = p.shape[-2], p.shape[-1], f.shape[-1]
+    ww = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    m = np.ascontiguousarray(mode, dtype=np.int32).reshape(-1)
+    iw = np.ascontiguousarray(interp_weight, dtype=np.float64).reshape(-1)
+    if ww.shape[0] != F:
+        raise ValueError("quantile_map: w must have one weight per forecast")
+    if m.shape[0] != T or iw.shape[0] != T:
+        raise ValueError("quantile_map: mode and interp_weight must have one entry per step")
+    out = np.empty(p.shape)
+    args = (B, T, F, P, _ptr(f), _ptr(ww), _ptr(p), _ptr(m), _ptr(iw), int(bool(interpolated)), _ptr(out))
+    if host:
+        check(L.shyft_hip_quantile_map_host(*args), None)
+    else:
+        check(L.shyft_hip_quantile_map(device, *args), None)
+    return out
+
+
+def quantile_map_last_path(device: int = -1) -> int:
+    """QM_PATH_WAVE or QM_PATH_GROUP: the launch shape of the last quantile_map kernel on the device."""
+    return int(lib().shyft_hip_quantile_map_last_path(device))
+
+
+def quantile_map_last_ms(device: int = -1) -> float:
+    """HIP-event milliseconds of the last quantile_map kernel on the device, copies excluded."""
+    return float(lib().shyft_hip_quantile_map_last_ms(device))
