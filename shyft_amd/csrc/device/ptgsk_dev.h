@@ -30,15 +30,20 @@ struct gs_state {
 // melt or reset, so most calls of calc_snow_state within a cell reuse it. The functions below take any cache
 // type with this get(): the kernel keeps the cache in its lane's LDS slots (lgamma_cache_lds) rather than in
 // registers that the step loop would spill around every call.
+// job_lgamma(shape) is the lgamma(a2) that gs_front hands to enqueue with a corr_lwc job.
 struct lgamma_cache {
     double a = -1.0, v = 0.0;
     __device__ inline double get(double shape) {
         if (shape != a) { a = shape; v = dlgamma(shape); }
         return v;
     }
+    __device__ inline double job_lgamma(double shape) { return get(shape); }
 };
 // a[threadIdx.x], v[threadIdx.x] of two workgroup arrays (the slot address is formed from threadIdx.x at each
 // use, not held in a register)
+// DEFER_JOB: job_lgamma only sets the slot's key and returns NaN; the wavefront that solves the job evaluates
+// dlgamma(a2) and fills the owner's slot before the owner reads it (kernels/ptgsk.hip)
+template <bool DEFER_JOB = false>
 struct lgamma_cache_lds {
     double* a;
     double* v;
@@ -46,6 +51,11 @@ struct lgamma_cache_lds {
         const int t = threadIdx.x;
         if (shape != a[t]) { a[t] = shape; v[t] = dlgamma(shape); }
         return v[t];
+    }
+    __device__ inline double job_lgamma(double shape) {
+        if (!DEFER_JOB) return get(shape);
+        a[threadIdx.x] = shape;
+        return __builtin_nan("");
     }
 };
 
@@ -122,8 +132,8 @@ __device__ inline double gs_calc_q(double a, double b, double z, double lga) {
 #endif
 // q1: Q1 = calc_q(a1, b1, z1) when the caller already has it (from the step's first calc_snow_state, gs_lw),
 // else NaN
-// lga2 = lgamma(a2): the job's lane evaluates it (its lgamma cache needs it for the step's calc_snow_state after
-// the solve anyway), so the solving wavefront does not
+// lga2 = lgamma(a2): the caller supplies it (the job's lane from its lgamma cache, or the kernel's solving wavefront
+// for all its jobs at once), since the owner's calc_snow_state after the solve wants it too
 __device__ __noinline__ double gs_corr_lwc(double z1, double a1, double b1, double a2, double b2,
                                            double q1, double lga2 SHYFT_PROF_NF) {
 #ifdef SHYFT_ABLATE_BRENT
@@ -230,11 +240,20 @@ struct gs_carry {
 // enqueue(z1, a1, b1, a2, b2, q1, lga2) receives the step's corr_lwc job where it arises (q1 = calc_q(a1, b1, z1)
 // or NaN, lga2 = lgamma(a2)): the kernel writes it straight into its workgroup's LDS job queue, so the seven job
 // values are not held in registers (or scratch) until a later queue pass
-template <class LGC, class Enqueue>
+// new_shape(shape) receives the shape that gs_back's final calc_snow_state of this step will use, on the lanes
+// where that call can need lgamma(shape) and the shape can be new. gs_back's alpha, sdc_melt_mean and sdc_scale do
+// not depend on the Brent result (only lwc does), so gs_front already has them: the snowfall update below, then
+// gs_back's melt update, restated here with its own expressions on the same values (the same bits). It is a
+// prediction for the caller's lgamma cache only (the kernel's 256-lane instances queue it for the wavefronts that
+// wait during the Brent phase): gs_back computes its own values and a shape not announced here is a cache miss that
+// evaluates in place. Not announced: a step that ends in reset_snow_pack (lwc = 0 and acc_melt = -1 there, so
+// calc_snow_state uses no incomplete gamma), a lane without liquid water at the end of the step (the same), and
+// the melt season (acc_melt >= 0: alpha does not change there). A no-op new_shape compiles to nothing.
+template <class LGC, class Enqueue, class NewShape>
 __device__ inline void gs_front(gs_state& s, gs_mid& m, bool start_melt, double dt_s, double dt_us,
                                       const double* __restrict__ P, const gs_cell& cc, double T, double rad,
                                       double prec_mm_h, double wind_speed, double rel_hum, LGC& lgc,
-                                      const gs_carry& carry, Enqueue&& enqueue) {
+                                      const gs_carry& carry, Enqueue&& enqueue, NewShape&& new_shape) {
     m.need = false;
     m.done = false;
     double sdc_melt_mean = s.sdc_melt_mean;
@@ -329,8 +348,19 @@ __device__ inline void gs_front(gs_state& s, gs_mid& m, bool start_melt, double 
                 // opening calc_snow_state's liquid-water pair (same shape, scale and point, z1 / b1 = sat / scale)
                 const double q1 = (sdc_scale_prev > 0.0 && lw.p == lw.p) ? a1 * b1 * lw.p1 + z1 * (1.0 - lw.p)
                                                                           : __builtin_nan("");
-                enqueue(z1, a1, b1, alpha, sdc_scale, q1, lgc.get(alpha));
+                enqueue(z1, a1, b1, alpha, sdc_scale, q1, lgc.job_lgamma(alpha));
             }
+        }
+        // the shape of gs_back's final calc_snow_state (its acc_melt < 0 branch, in its words)
+        if (!(sdc_melt_mean <= potential_melt)) {
+            double lwc_end = lwc + rain;  // (a job lane's lwc is the Brent result: it always announces)
+            double shape = alpha;
+            if (potential_melt > 0.0) {
+                lwc_end += potential_melt;
+                shape = smax(0.1, (sdc_melt_mean - potential_melt) / sdc_scale);
+                if (shape > cc.inv_cv2) shape = cc.inv_cv2;
+            }
+            if (m.need || lwc_end > 0.0) new_shape(shape);
         }
     }
     (void)sca;  // (its value is dead: gs_back's final calc_snow_state assigns sca)
@@ -345,6 +375,15 @@ __device__ inline void gs_front(gs_state& s, gs_mid& m, bool start_melt, double 
     s.sdc_melt_mean = sdc_melt_mean;
     s.acc_melt = acc_melt;
     // (lwc and temp_swe are unchanged until gs_back)
+}
+
+template <class LGC, class Enqueue>
+__device__ inline void gs_front(gs_state& s, gs_mid& m, bool start_melt, double dt_s, double dt_us,
+                                      const double* __restrict__ P, const gs_cell& cc, double T, double rad,
+                                      double prec_mm_h, double wind_speed, double rel_hum, LGC& lgc,
+                                      const gs_carry& carry, Enqueue&& enqueue) {
+    gs_front(s, m, start_melt, dt_s, dt_us, P, cc, T, rad, prec_mm_h, wind_speed, rel_hum, lgc, carry, enqueue,
+             [](double) {});
 }
 
 template <class LGC>

@@ -39,9 +39,9 @@ extern "C" int shyft_ptgsk_prof_read(unsigned long long* out) {
     unsigned long long z[12] = {};
     return hipMemcpyToSymbol(HIP_SYMBOL(g_ptgsk_prof), z, sizeof z) != hipSuccess;
 }
-#define PROF_DECL unsigned long long prof_acc[6] = {0, 0, 0, 0, 0, 0}; unsigned long long prof_t = __builtin_amdgcn_s_memtime();
+#define PROF_DECL unsigned long long prof_acc[6] = {0, 0, 0, 0, 0, 0}, prof_lg = 0; unsigned long long prof_t = __builtin_amdgcn_s_memtime();
 #define PROF_MARK(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); prof_acc[k] += t_ - prof_t; prof_t = t_; } while (0)
-#define PROF_FLUSH() do { if ((threadIdx.x & 63) == 0) for (int k_ = 0; k_ < 6; ++k_) atomicAdd(&g_ptgsk_prof[k_], prof_acc[k_]); } while (0)
+#define PROF_FLUSH() do { if ((threadIdx.x & 63) == 0) { for (int k_ = 0; k_ < 6; ++k_) atomicAdd(&g_ptgsk_prof[k_], prof_acc[k_]); atomicAdd(&g_ptgsk_prof[11], prof_lg); } } while (0)
 #else
 #define PROF_DECL
 #define PROF_MARK(k) ((void)0)
@@ -74,6 +74,24 @@ constexpr int BLOCK = 256;
 
 // issue priority (s_setprio) of the Brent-solving wavefront: 138.2 -> 134.5 ms per chunk (year mean, 1M cells)
 constexpr int BRENT_PRIO = 3;
+
+// the lgamma queue of the 256-lane instances (LGQ below; 0: every lane evaluates its new shapes in place, for A/B
+// builds), and what a step with queued shapes and no Brent job does: 0, the owners evaluate their own shape in
+// place (no second barrier, as without the queue); n > 0, from n queued shapes on all four wavefronts evaluate the
+// compacted list and a second barrier follows (profiles/r06/ptgsk_lgamma_queue_ab.txt)
+#ifndef SHYFT_PTGSK_LGQ
+#define SHYFT_PTGSK_LGQ 1
+#endif
+#ifndef SHYFT_PTGSK_LGQ_NOBRENT
+#define SHYFT_PTGSK_LGQ_NOBRENT 0
+#endif
+// 1: the lgamma(a2) of a Brent job is evaluated by the wavefront that solves the job, ahead of its solves, and
+// written to the owner's cache slot; 0: by every wavefront that holds a job lane, in gs_front (as before the queue).
+// r06, 1M cells, 20 x 438 steps, 5 alternating runs: parent 10.212e9 - 10.249e9 cell-steps/s, the queue alone
+// 10.321e9 - 10.336e9, with this 10.412e9 - 10.449e9, bit-exact (profiles/r06/ptgsk_lgamma_queue_ab.txt)
+#ifndef SHYFT_PTGSK_LGQ_JOBLG
+#define SHYFT_PTGSK_LGQ_JOBLG 1
+#endif
 
 // UNIFORM: every cell of the launch uses parameter set 0 (the region parameter, no catchment overrides):
 // the parameter row is then wave-uniform and lives in SGPRs (scalar loads), which frees the VGPRs the
@@ -166,7 +184,9 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
     double q = st[PS_KIRCHNER_Q * N + lc];
     lcc[9][threadIdx.x] = -1.0;  // the lgamma cache (device/ptgsk_dev.h)
     lcc[10][threadIdx.x] = 0.0;
-    lgamma_cache_lds lgc{lcc[9], lcc[10]};
+    constexpr bool LGQ = SHYFT_PTGSK_LGQ != 0 && B == 256 && !SPEC;
+    constexpr bool JOBLG = LGQ && SHYFT_PTGSK_LGQ_JOBLG != 0;
+    lgamma_cache_lds<JOBLG> lgc{lcc[9], lcc[10]};
     gs_carry carry;
     int32_t err = 0;
 
@@ -190,10 +210,23 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
     __shared__ double jz1[B], ja1[B], jb1[B], ja2[B], jb2[B], jq1[B], jlg2[B], jres[B];
     __shared__ double jsz[SPEC ? 64 : 1], jsf[SPEC ? 64 : 1];  // speculative opening: point and f of lane t
     __shared__ int jcount[2];
+    // lgamma queue of the workgroup (LGQ): the lanes whose final calc_snow_state of the step will want lgamma of a
+    // shape their cache slot does not hold (gs_front's new_shape, device/ptgsk_dev.h). The owner writes the shape
+    // into its key slot lcc[9][t] and its lane id into lq; between the step's two barriers the wavefronts that are
+    // not solving Brent jobs evaluate dlgamma of the queued shapes, one per lane, into the owners' value slots
+    // lcc[10][owner], so the owners' gs_back hits the cache instead of every wavefront running dlgamma for a few
+    // of its lanes. Invariant: a slot whose key has been set holds dlgamma(key) by the time its owner next reads it
+    // (DESIGN.md 3.1). The same function of the same argument: the same bits as the owner's own evaluation.
+    __shared__ unsigned short lq[LGQ ? B : 1];
+    __shared__ unsigned short jown[JOBLG ? B : 1];  // JOBLG: the lane that owns job j
+    __shared__ int lcount[2];
     __shared__ int wsimd[B / 64];
     publish_wave_simd(wsimd);
     if (COMPACT) {
-        if (threadIdx.x == 0) jcount[0] = jcount[1] = 0;  // both: the first step may be odd (start_step)
+        if (threadIdx.x == 0) {  // both: the first step may be odd (start_step)
+            jcount[0] = jcount[1] = 0;
+            if (LGQ) lcount[0] = lcount[1] = 0;
+        }
         __syncthreads();
     }
     // the lane that solves job 0: the first lane of the solving wavefront (device/wave_place.h)
@@ -240,32 +273,81 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
         m.need = false;
         m.done = true;
         LOAD_GCELL();
-        if (threadIdx.x == 0) jcount[(i + 1) & 1] = 0;  // next step's counter (race-free: see DESIGN.md)
+        if (threadIdx.x == 0) {  // next step's counters (race-free: see DESIGN.md)
+            jcount[(i + 1) & 1] = 0;
+            if (LGQ) lcount[(i + 1) & 1] = 0;
+        }
         int slot = -1;
+        bool queued = false;  // this lane has a shape in the step's lgamma queue
+        auto new_shape = [&](double shape) {
+            if (LGQ && shape != lcc[9][threadIdx.x]) {
+                lq[atomicAdd(&lcount[i & 1], 1)] = (unsigned short)threadIdx.x;
+                lcc[9][threadIdx.x] = shape;
+                queued = true;
+            }
+        };
+        // JOBLG: the jobs' lgamma(a2) ahead of the solves, by the lane that solves the job; it also goes to the
+        // owner's slot unless the owner has queued another shape since (the keys are final after the first barrier)
+        auto brent_jobs = [&](int first, int nj) {
+            if (JOBLG)
+                for (int j = first; j < nj; j += B) {
+                    const double lga2 = dlgamma(ja2[j]);
+                    jlg2[j] = lga2;
+                    const int o = jown[j];
+                    if (lcc[9][o] == ja2[j]) lcc[10][o] = lga2;
+                }
+            for (int j = first; j < nj; j += B)
+                jres[j] = GS_BRENT_JOB(jz1[j], ja1[j], jb1[j], ja2[j], jb2[j], jq1[j], jlg2[j]);
+        };
+        // dlgamma of the queued shapes first, first + stride, ... into their owners' value slots
+        auto lgamma_jobs = [&](int first, int stride, int nl) {
+            for (int j = first; j < nl; j += stride) {
+                const int o = lq[j];
+                lcc[10][o] = dlgamma(lcc[9][o]);
+            }
+        };
         // the step's Brent job goes into the queue where gs_front forms it
         auto enqueue = [&](double z1, double a1, double b1, double a2, double b2, double q1, double lga2) {
             slot = atomicAdd(&jcount[i & 1], 1);
             jz1[slot] = z1; ja1[slot] = a1; jb1[slot] = b1; ja2[slot] = a2; jb2[slot] = b2;
             jq1[slot] = q1; jlg2[slot] = lga2;
+            if (JOBLG) jown[slot] = (unsigned short)threadIdx.x;
         };
 #ifndef SHYFT_ABLATE_SNOW
         if (valid)
-            gs_front(s, m, start_melt, a.dt_s, a.dt_us, P, gcell, temp, rad, prec, wind_speed, rel_hum, lgc, carry, enqueue);
+            gs_front(s, m, start_melt, a.dt_s, a.dt_us, P, gcell, temp, rad, prec, wind_speed, rel_hum, lgc, carry, enqueue,
+                     new_shape);
 #endif
         PROF_MARK(0);  // forcing + gs_front
         double z = 0.0;
         {
             __syncthreads();
             PROF_MARK(1);  // job queue + barrier
+            // both counts are uniform: written before the barrier above, and not rewritten before the next step's
+            // first barrier (thread 0 zeroes the other pair)
             const int nj = jcount[i & 1];
+            const int nl = LGQ ? lcount[i & 1] : 0;
+            // the wavefronts behind the solving ones (lanes ns .. B-1 in the solver's lane order t) evaluate the
+            // queued shapes during the Brent phase, at priority 0; when every wavefront solves, all of them do it
+            // after their jobs. Either way before the second barrier, after which the owners read their slots.
+            auto lgamma_phase = [&](int t) {
+                const int ns = (nj + 63) & ~63;
+                if (ns >= B) lgamma_jobs(t, B, nl);
+                else if (t >= ns) lgamma_jobs(t - ns, B - ns, nl);
+            };
             if (nj > 0) {
 #ifdef SHYFT_PROF
                 const unsigned long long tb = __builtin_amdgcn_s_memtime();
                 if (threadIdx.x < nj) __builtin_amdgcn_s_setprio(BRENT_PRIO);
-                for (int j = threadIdx.x; j < nj; j += B) jres[j] = GS_BRENT_JOB(jz1[j], ja1[j], jb1[j], ja2[j], jb2[j], jq1[j], jlg2[j]);
+                brent_jobs((int)threadIdx.x, nj);
                 __builtin_amdgcn_s_setprio(0);
                 if (threadIdx.x < nj && (threadIdx.x & 63) == 0)
                     atomicAdd(&g_ptgsk_prof[8], (unsigned long long)(__builtin_amdgcn_s_memtime() - tb));
+                if (LGQ && nl > 0) {
+                    const unsigned long long tl = __builtin_amdgcn_s_memtime();
+                    lgamma_phase((int)threadIdx.x);
+                    prof_lg += __builtin_amdgcn_s_memtime() - tl;  // ([11]: summed per wavefront, flushed at the end)
+                }
 #else
                 const int t = SPEC ? (int)threadIdx.x : (int)((threadIdx.x - jrot) & (B - 1));
                 // the solving wavefront is the workgroup's critical path (its other wavefronts wait at the
@@ -293,9 +375,10 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
                         jres[t] = gs_corr_lwc_memo(jz1[t], ja1[t], jb1[t], ja2[t], jb2[t], jq1[t], jlg2[t], mm);
                     }
                 } else {
-                    for (int j = t; j < nj; j += B) jres[j] = GS_BRENT_JOB(jz1[j], ja1[j], jb1[j], ja2[j], jb2[j], jq1[j], jlg2[j]);
+                    brent_jobs(t, nj);
                 }
                 __builtin_amdgcn_s_setprio(0);
+                if (LGQ && nl > 0) lgamma_phase(t);
 #endif
                 __syncthreads();
                 // test knob: the other wavefronts read their results late, so a fast first wavefront is already
@@ -303,6 +386,15 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
                 if (!LEAN && a.read_delay > 0 && (threadIdx.x >> 6) != 0)
                     for (int k = 0; k < a.read_delay; ++k) __builtin_amdgcn_s_sleep(127);
                 if (slot >= 0) z = jres[slot];
+            } else if (LGQ && SHYFT_PTGSK_LGQ_NOBRENT > 0 && nl >= SHYFT_PTGSK_LGQ_NOBRENT) {
+                // no Brent job and many shapes: all four wavefronts evaluate the compacted list, then the barrier
+                // (a wavefront that reads nl late, after thread 0 zeroed it for the step after next, reads 0 only
+                // where the others read less than the threshold: with the barrier here nobody is a step ahead)
+                lgamma_jobs((int)threadIdx.x, B, nl);
+                __syncthreads();
+            } else if (LGQ && queued) {
+                // no Brent job: nobody waits, so the owner evaluates its own shape (no second barrier, as before)
+                lcc[10][threadIdx.x] = dlgamma(lcc[9][threadIdx.x]);
             }
         }
         PROF_MARK(2);  // Brent phase

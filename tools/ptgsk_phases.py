@@ -37,5 +37,8 @@ for s in range(12):
     if buf[9]:
         # solver waves: cycles per Brent loop trip (wave max of f evaluations), and useful lanes per trip
         extra = f"  solver: {buf[8] / buf[9]:7.0f} cyc/trip, {buf[10] / buf[9]:4.1f} lane-evals/trip"
+    if buf[11]:
+        # the lgamma queue's evaluations inside the Brent phase (all wavefronts, helpers and solvers)
+        extra += f"  lgamma queue {100.0 * buf[11] / tot:4.1f}%"
     print(f"chunk {s:2d} {r.last_run_ms():6.1f} ms  " +
           "  ".join(f"{n} {100.0 * buf[k] / tot:4.1f}%" for k, n in enumerate(names)) + extra, flush=True)
