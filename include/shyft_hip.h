@@ -404,6 +404,52 @@ int shyft_hip_quantile_map_last_path(int device);
  * counterpart in core/time_series_qm.h: measurement only.) */
 double shyft_hip_quantile_map_last_ms(int device);
 
+/* S point series resampled onto the fixed_dt axis (ta_t0, ta_dt, T) in one launch of kernels/resample.hip on a device
+ * (device < 0 = current); it replaces one average_accessor / integral_ts / accumulate_ts pass per series. Host
+ * pointers, stateless. The series are in CSR form: row [S+1] point offsets (row[0] == 0), t [row[S]] point times in
+ * int64 microseconds, v [row[S]] values, t_end [S] the end of each series' last interval, fx [S] POINT_INSTANT_VALUE
+ * (0, linear between points) or POINT_AVERAGE_VALUE (1, stair-case). out is [T][S], series fastest. mode:
+ *  AVERAGE     average_accessor::value(i) with USE_NAN (core/time_series.h:2033-2072 over average_value :302-306 and
+ *              accumulate_value :202-288): NaN for a period that starts at or after the series' end, else the area of
+ *              the non-NaN parts divided by to_seconds of their time;
+ *  INTEGRAL    integral_ts::value(i) (core/time_series_dd.h:532-538): that area, NaN when no time is covered; no
+ *              end-of-series rule;
+ *  ACCUMULATE  accumulate_ts::values() (core/time_series_dd.h:672-679), accumulate_accessor::value(i) in ascending i
+ *              (core/time_series.h:2100-2120): 0.0 at step 0, NaN once time(i) >= the series' end, else the running
+ *              sum of the areas of [time(i-1), time(i)), added in that order; a NaN stays.
+ * A series with no points gives NaN (ACCUMULATE: 0.0 at step 0, NaN after). Checked on the host before the launch,
+ * with the texts of host/time_series.hpp point_ts (core/time_axis.h:271-293): times increase strictly within a row
+ * ("time_axis::point_dt() needs time-points in increasing order"), t_end lies after the last point
+ * ("time_axis::point_dt() illegal end-of-axis"), ta_dt > 0. A one-point series whose point lies strictly inside a period is an error, as in the
+ * reference (accumulate_value asks point_dt::time for point 1, which throws). S == 0 or T == 0 returns 0 and launches
+ * nothing. Every operation is evaluated as written (int64 ticks, to_seconds as a division, no FMA), so the result is
+ * bit-identical to shyft_hip_resample_host. */
+#define SHYFT_HIP_RESAMPLE_AVERAGE 0
+#define SHYFT_HIP_RESAMPLE_INTEGRAL 1
+#define SHYFT_HIP_RESAMPLE_ACCUMULATE 2
+int shyft_hip_resample(int device, int mode, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                       const int64_t* t_end, const int32_t* fx, int64_t ta_t0, int64_t ta_dt, size_t T, double* out);
+/* The same values from average_values / accumulate_value of host/time_series.hpp (the restatement of
+ * core/time_series.h:202-310, 2033-2072) and a literal accumulate_accessor loop (:2100-2120); no device call, `device`
+ * is not used. */
+int shyft_hip_resample_host(int device, int mode, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                            const int64_t* t_end, const int32_t* fx, int64_t ta_t0, int64_t ta_dt, size_t T,
+                            double* out);
+/* HIP-event milliseconds of the kernel or kernels of the last shyft_hip_resample on this device (device < 0 =
+ * current), copies excluded. (No reference counterpart: measurement only.) */
+double shyft_hip_resample_last_ms(int device);
+/* The number of shyft_hip_resample calls that launched on this device so far. (No reference counterpart: test aid.) */
+uint64_t shyft_hip_resample_calls(int device);
+/* The launch shape of the (series, interval) kernel: DIRECT, one lane per job and its own store; TILED, a workgroup
+ * per 16 series x 64 intervals, lanes interval-fastest, stored series-fastest through LDS. AUTO takes TILED from 64
+ * intervals on. set_path is process-wide; last_path reports what the last call on the device ran. (No reference
+ * counterpart: test and measurement aid.) */
+#define SHYFT_HIP_RESAMPLE_PATH_AUTO 0
+#define SHYFT_HIP_RESAMPLE_PATH_DIRECT 1
+#define SHYFT_HIP_RESAMPLE_PATH_TILED 2
+int shyft_hip_resample_set_path(int path);
+int shyft_hip_resample_last_path(int device);
+
 size_t shyft_hip_number_of_catchments(const shyft_hip_region* h);
 int shyft_hip_catchment_ids(const shyft_hip_region* h, int64_t* cids);
 

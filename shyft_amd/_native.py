@@ -70,6 +70,14 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "shyft_hip_quantile_map_last_path": (C.c_int, [C.c_int]),
     "shyft_hip_quantile_map_last_ms": (C.c_double, [C.c_int]),
+    "shyft_hip_resample": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int64, C.c_int64, C.c_size_t, C.c_void_p]),
+    "shyft_hip_resample_host": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_int64, C.c_size_t, C.c_void_p]),
+    "shyft_hip_resample_last_ms": (C.c_double, [C.c_int]),
+    "shyft_hip_resample_calls": (C.c_uint64, [C.c_int]),
+    "shyft_hip_resample_set_path": (C.c_int, [C.c_int]),
+    "shyft_hip_resample_last_path": (C.c_int, [C.c_int]),
     "shyft_hip_synthetic_elevation": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]),
     "shyft_hip_run_cells": (C.c_int, [_h, C.c_size_t, C.c_int, C.c_int]),
     "shyft_hip_run_cells_async": (C.c_int, [_h, C.c_int, C.c_int]),

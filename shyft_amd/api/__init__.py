@@ -170,6 +170,56 @@ class TimeSeries:
         """true average onto a fixed_dt axis (average_accessor, time_series.h:2033-2072)."""
         return TimeSeries(ta, self._ts.average(ta), POINT_AVERAGE_VALUE)
 
+    def integral(self, ta):
+        """the integral (value x seconds) of the non-NaN parts of every interval of a fixed_dt axis (integral_ts,
+        time_series_dd.h:512-538), on the host."""
+        return _resampled([self], ta, _RESAMPLE_INTEGRAL, True)[0]
+
+    def accumulate(self, ta):
+        """the integral from the start of a fixed_dt axis to each of its time points: 0.0 first, NaN from the end of
+        the series on (accumulate_ts, time_series_dd.h:633-679), on the host."""
+        return _resampled([self], ta, _RESAMPLE_ACCUMULATE, True)[0]
+
+
+# ---- average / integral / accumulate of a set of series in one call (region.resample) -------------------------------
+_RESAMPLE_AVERAGE, _RESAMPLE_INTEGRAL, _RESAMPLE_ACCUMULATE = 0, 1, 2  # region.RESAMPLE_*
+
+
+def _resampled(tsv, ta, mode, host):
+    """every series of tsv onto ta by one region.resample call; the result's point type is the reference's
+    (time_series_dd.h:466, :525, :646)"""
+    from ..region import resample
+    values = resample([ts._ts for ts in tsv], ta, mode, host=host)
+    fx = POINT_INSTANT_VALUE if mode == _RESAMPLE_ACCUMULATE else POINT_AVERAGE_VALUE
+    out = TsVector()
+    for k in range(values.shape[1]):
+        out.append(TimeSeries(_impl=_api._PointTs(ta, values[:, k], fx)))
+    return out
+
+
+def _resample_any(ts, ta, mode, host):
+    if isinstance(ts, TimeSeries):
+        return _resampled([ts], ta, mode, True)[0]
+    return _resampled(ts, ta, mode, host)
+
+
+def average(ts, time_axis, *, host=False):
+    """api.average: the true average of a TimeSeries (on the host) or of every series of a TsVector (one device
+    call) on time_axis; POINT_AVERAGE_VALUE."""
+    return _resample_any(ts, time_axis, _RESAMPLE_AVERAGE, host)
+
+
+def integral(ts, time_axis, *, host=False):
+    """api.integral: the integral over every interval of time_axis, of a TimeSeries (on the host) or of every series
+    of a TsVector (one device call); POINT_AVERAGE_VALUE."""
+    return _resample_any(ts, time_axis, _RESAMPLE_INTEGRAL, host)
+
+
+def accumulate(ts, time_axis, *, host=False):
+    """api.accumulate: the integral from the start of time_axis to each time point, of a TimeSeries (on the host) or
+    of every series of a TsVector (one device call); POINT_INSTANT_VALUE."""
+    return _resample_any(ts, time_axis, _RESAMPLE_ACCUMULATE, host)
+
 
 # ---- percentiles of a set of series (core/time_series_statistics.h:107-246; api_time_series.cpp) ---------------------
 class statistics_property:  # time_series_statistics.h:107-111
@@ -249,6 +299,21 @@ class TsVector(_Vector):
 
     def percentiles(self, time_axis, percentiles):
         return _percentiles_of(self, time_axis, percentiles)
+
+    def average(self, ta, *, host=False):
+        """the true average of every series on a fixed_dt axis, all in one device call (region.resample), or with
+        host=True on the host, bit-identical; a TsVector of POINT_AVERAGE_VALUE series on ta."""
+        return _resampled(self, ta, _RESAMPLE_AVERAGE, host)
+
+    def integral(self, ta, *, host=False):
+        """the integral of every series over every interval of a fixed_dt axis, in one device call, or with host=True
+        on the host, bit-identical; a TsVector of POINT_AVERAGE_VALUE series on ta."""
+        return _resampled(self, ta, _RESAMPLE_INTEGRAL, host)
+
+    def accumulate(self, ta, *, host=False):
+        """the integral of every series from the start of a fixed_dt axis to each of its time points, in one device
+        call, or with host=True on the host, bit-identical; a TsVector of POINT_INSTANT_VALUE series on ta."""
+        return _resampled(self, ta, _RESAMPLE_ACCUMULATE, host)
 
 
 class TsFactory:

@@ -585,6 +585,31 @@ PYBIND11_MODULE(_api, m) {
             return py::array_t<double>(v.size(), v.data());
         });
     }
+    // The host work of region.resample: the point series of a list as the CSR arrays of shyft_hip_resample (row, t, v,
+    // t_end, fx) and the axis in microseconds (t0, dt, n).
+    m.def("_resample_plan", [](const py::list& series, const fixed_dt& ta) {
+        std::vector<const point_ts*> src;
+        for (auto h : series) src.push_back(&h.cast<const point_ts&>());
+        const size_t S = src.size();
+        const py::ssize_t n_series = py::ssize_t(S);
+        py::array_t<int64_t> row(n_series + 1), t_end(n_series);
+        py::array_t<int32_t> fx(n_series);
+        int64_t* r = row.mutable_data();
+        r[0] = 0;
+        for (size_t s = 0; s < S; ++s) {
+            r[s + 1] = r[s] + int64_t(src[s]->size());
+            t_end.mutable_data()[s] = src[s]->t_end;
+            fx.mutable_data()[s] = int32_t(src[s]->fx);
+        }
+        const py::ssize_t n_points = py::ssize_t(r[S]);
+        py::array_t<int64_t> t(n_points);
+        py::array_t<double> v(n_points);
+        for (size_t s = 0; s < S; ++s) {
+            std::copy(src[s]->t.begin(), src[s]->t.end(), t.mutable_data() + r[s]);
+            std::copy(src[s]->v.begin(), src[s]->v.end(), v.mutable_data() + r[s]);
+        }
+        return py::make_tuple(row, t, v, t_end, fx, int64_t(ta.t), int64_t(ta.dt), ta.size());
+    });
     py::class_<interpolation_parameter>(m, "InterpolationParameter")
         .def(py::init<>())
         .def(py::init([](const btk_parameter& t, const idw_precipitation_parameter& p, const idw_parameter& ws,

@@ -909,18 +909,44 @@ class region_model {
         throw_if(shyft_hip_set_collection(h_.get(), mode, any_state ? 1 : 0), h_.get());
     }
 
+    // The sources on the model axis, vals[t * S + s]: average_accessor::value(t) of every source
+    // (region_model.h:135-145), all in one shyft_hip_resample call on the region's device (shard 0's device for a
+    // sharded region). Bit-identical to average_values() of each source.
+    std::vector<double> source_values(const std::vector<geo_point_ts>& src) const {
+        const size_t S = src.size(), T = time_axis.size();
+        std::vector<int64_t> row(S + 1, 0), t_end(S);
+        std::vector<int32_t> fx(S);
+        for (size_t s = 0; s < S; ++s) {
+            row[s + 1] = row[s] + int64_t(src[s].ts.size());
+            t_end[s] = src[s].ts.t_end;
+            fx[s] = int32_t(src[s].ts.fx);
+        }
+        std::vector<int64_t> t(size_t(row[S]));
+        std::vector<double> v(size_t(row[S]));
+        for (size_t s = 0; s < S; ++s) {
+            std::copy(src[s].ts.t.begin(), src[s].ts.t.end(), t.begin() + row[s]);
+            std::copy(src[s].ts.v.begin(), src[s].ts.v.end(), v.begin() + row[s]);
+        }
+        std::vector<double> vals(T * S);
+        int device = -1;
+        shyft_hip_region_shards(h_.get(), 0, &device, nullptr, nullptr);
+        throw_if(shyft_hip_resample(device, SHYFT_HIP_RESAMPLE_AVERAGE, S, row.data(), t.data(), v.data(), t_end.data(),
+                                    fx.data(), time_axis.t, time_axis.dt, T, vals.data()),
+                 nullptr);
+        return vals;
+    }
+
     void run_idw(int var, const std::vector<geo_point_ts>& src, const idw_parameter& p, double gradient, bool by_eq,
                  double scale) {
         if (src.empty()) return;
         const size_t S = src.size(), T = time_axis.size();
-        std::vector<double> xyz(3 * S), vals(T * S);
+        std::vector<double> xyz(3 * S);
         for (size_t s = 0; s < S; ++s) {
             xyz[3 * s] = src[s].mid_point.x;
             xyz[3 * s + 1] = src[s].mid_point.y;
             xyz[3 * s + 2] = src[s].mid_point.z;
-            auto v = average_values(src[s].ts, time_axis);
-            for (size_t t = 0; t < T; ++t) vals[t * S + s] = v[t];
         }
+        const std::vector<double> vals = source_values(src);
         const double prm[7] = {double(p.max_members), p.max_distance, p.distance_measure_factor, p.zscale,
                                gradient, by_eq ? 1.0 : 0.0, scale};
         throw_if(shyft_hip_interpolate(h_.get(), var, S, xyz.data(), vals.data(), 0, T, prm), h_.get());
@@ -929,14 +955,13 @@ class region_model {
     // btk::btk_interpolation over the device (bayesian_kriging.h:280-402), sources averaged onto the axis
     void run_btk(const std::vector<geo_point_ts>& src, const btk_parameter& p) {
         const size_t S = src.size(), T = time_axis.size();
-        std::vector<double> xyz(3 * S), vals(T * S), prior(T), prm(5);
+        std::vector<double> xyz(3 * S), prior(T), prm(5);
         for (size_t s = 0; s < S; ++s) {
             xyz[3 * s] = src[s].mid_point.x;
             xyz[3 * s + 1] = src[s].mid_point.y;
             xyz[3 * s + 2] = src[s].mid_point.z;
-            auto v = average_values(src[s].ts, time_axis);
-            for (size_t t = 0; t < T; ++t) vals[t * S + s] = v[t];
         }
+        const std::vector<double> vals = source_values(src);
         for (size_t t = 0; t < T; ++t) prior[t] = p.temperature_gradient(time_axis.period(t));
         p.as_abi(prm.data());
         throw_if(shyft_hip_interpolate_btk(h_.get(), S, xyz.data(), vals.data(), 0, T, prior.data(), prm.data()),

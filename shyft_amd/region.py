@@ -546,3 +546,62 @@ def quantile_map_last_path(device: int = -1) -> int:
 def quantile_map_last_ms(device: int = -1) -> float:
     """HIP-event milliseconds of the last quantile_map kernel on the device, copies excluded."""
     return float(lib().shyft_hip_quantile_map_last_ms(device))
+
+
+RESAMPLE_AVERAGE, RESAMPLE_INTEGRAL, RESAMPLE_ACCUMULATE = 0, 1, 2
+RESAMPLE_PATH_AUTO, RESAMPLE_PATH_DIRECT, RESAMPLE_PATH_TILED = 0, 1, 2
+
+
+def resample(series, time_axis, mode: int = RESAMPLE_AVERAGE, device: int = -1, host: bool = False) -> np.ndarray:
+    """S point series onto a fixed_dt axis in one call (shyft_hip_resample; core/time_series.h:202-310, 2033-2120,
+    core/time_series_dd.h:532-538, 672-679). series is a list of the api's `_PointTs`, time_axis a
+    TimeAxisFixedDeltaT; mode RESAMPLE_AVERAGE (the true average, NaN from the series' end on), RESAMPLE_INTEGRAL
+    (the integral of each interval) or RESAMPLE_ACCUMULATE (0.0, then the running integral from the axis' start, NaN
+    from the series' end on). host=True evaluates the same values with the host's average_values / accumulate_value
+    (shyft_hip_resample_host), which the device result is bit-identical to. Returns [T][S], series fastest."""
+    from .api import _api
+    row, t, v, t_end, fx, t0, dt, T = _api._resample_plan(list(series), time_axis)
+    return resample_csr(row, t, v, t_end, fx, t0, dt, T, mode, device=device, host=host)
+
+
+def resample_csr(row, t, v, t_end, fx, ta_t0: int, ta_dt: int, T: int, mode: int = RESAMPLE_AVERAGE, device: int = -1,
+                 host: bool = False) -> np.ndarray:
+    """resample on the arrays of the C ABI: row [S+1] point offsets, t [row[S]] int64 microseconds, v [row[S]],
+    t_end [S] int64 microseconds, fx [S] (0 POINT_INSTANT_VALUE, 1 POINT_AVERAGE_VALUE), and the axis in
+    microseconds. Returns [T][S]."""
+    row = np.ascontiguousarray(row, dtype=np.int64).reshape(-1)
+    t = np.ascontiguousarray(t, dtype=np.int64).reshape(-1)
+    v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+    t_end = np.ascontiguousarray(t_end, dtype=np.int64).reshape(-1)
+    fx = np.ascontiguousarray(fx, dtype=np.int32).reshape(-1)
+    S = row.shape[0] - 1
+    if S < 0 or t_end.shape[0] != S or fx.shape[0] != S:
+        raise ValueError("resample: row must have one entry more than t_end and fx")
+    if t.shape[0] != v.shape[0] or (S and (row[0] != 0 or row[-1] != t.shape[0])):
+        raise ValueError("resample: row must run from 0 to the number of points")
+    out = np.empty((int(T), S), dtype=np.float64)
+    fn = lib().shyft_hip_resample_host if host else lib().shyft_hip_resample
+    check(fn(device, int(mode), S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), int(ta_t0), int(ta_dt), int(T),
+             _ptr(out)), None)
+    return out
+
+
+def resample_last_ms(device: int = -1) -> float:
+    """HIP-event milliseconds of the kernel or kernels of the last resample on the device, copies excluded."""
+    return float(lib().shyft_hip_resample_last_ms(device))
+
+
+def resample_calls(device: int = -1) -> int:
+    """The number of resample calls that launched on the device so far."""
+    return int(lib().shyft_hip_resample_calls(device))
+
+
+def resample_set_path(path: int) -> None:
+    """RESAMPLE_PATH_DIRECT or RESAMPLE_PATH_TILED forces the launch shape of resample for the process,
+    RESAMPLE_PATH_AUTO gives the choice back (test and measurement aid)."""
+    check(lib().shyft_hip_resample_set_path(int(path)), None)
+
+
+def resample_last_path(device: int = -1) -> int:
+    """RESAMPLE_PATH_DIRECT or RESAMPLE_PATH_TILED: the launch shape of the last resample on the device."""
+    return int(lib().shyft_hip_resample_last_path(device))
