@@ -450,6 +450,70 @@ uint64_t shyft_hip_resample_calls(int device);
 int shyft_hip_resample_set_path(int path);
 int shyft_hip_resample_last_path(int device);
 
+/* Observation preparation of S point series in one device call each (kernels/tsprep.hip; device < 0 = current). Host
+ * pointers, stateless. The series are in the CSR form of shyft_hip_resample (row [S+1], t and v [row[S]], t_end [S],
+ * fx [S]) and are checked in the same way and with the same texts before anything is launched: row[0] == 0 and
+ * non-decreasing, times strictly increasing in a series, t_end after the last point, times within a quarter of the
+ * 64-bit range. out holds one double per input point (per query for ice-packing) in the same CSR order. A refused
+ * batch launches nothing; S == 0 or zero points (queries) returns 0 and launches nothing. Every operation is
+ * evaluated as written (int64 ticks, to_seconds as a division, no FMA, detmath exp and pow), so each entry is
+ * bit-identical to its _host twin, which runs host/ts_prep.hpp on one thread and does not use `device`.
+ *
+ * shyft_hip_ts_rating_curve replaces rating_curve_ts::value(i) = rating_curve_parameters::flow(time(i), value(i))
+ * per series (core/time_series.h:1493-1506, 1395-1408, 1641-1644). The parameter packs are a three-level CSR:
+ * pack_row [P+1] offsets into curve_t [C] (the start times of a pack's curves, strictly increasing in a pack),
+ * curve_row [C+1] offsets into seg [G][4] = lower, a, b, c (sorted on lower in a curve); pack_of [S] is the pack of
+ * each series. NaN before the first curve, below the first segment and for a pack without curves; a curve without
+ * segments that a point would use is refused with the reference's "no rating-curve segments". */
+int shyft_hip_ts_rating_curve(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                              const int64_t* t_end, const int32_t* fx, size_t P, const int64_t* pack_row,
+                              const int64_t* curve_t, const int64_t* curve_row, const double* seg, const int64_t* pack_of,
+                              double* out);
+int shyft_hip_ts_rating_curve_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                                   const int64_t* t_end, const int32_t* fx, size_t P, const int64_t* pack_row,
+                                   const int64_t* curve_t, const int64_t* curve_row, const double* seg,
+                                   const int64_t* pack_of, double* out);
+/* shyft_hip_ts_ice_packing replaces ice_packing_ts::detect_ice_packing(t) per query (core/time_series.h:1808-1831;
+ * value(i) and operator()(t)): 1.0 when the average temperature over [t - window, t) lies below the threshold, 0.0
+ * when not or when the period is empty, NaN when it cannot be told under the policy (0 DISALLOW_MISSING,
+ * 1 ALLOW_INITIAL_MISSING, 2 ALLOW_ANY_MISSING). The series are the temperatures; the query times are a CSR of their
+ * own, qrow [S+1] and qt [qrow[S]], so the series' own points and any other axis are served alike. window [S] (ticks,
+ * >= 0), threshold [S], policy [S]. out is [qrow[S]]. A one-point series queried under DISALLOW_MISSING with a window
+ * that starts before the point and holds it is an error, as in the reference (point_dt::time throws). */
+int shyft_hip_ts_ice_packing(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                             const int64_t* t_end, const int32_t* fx, const int64_t* qrow, const int64_t* qt,
+                             const int64_t* window, const double* threshold, const int32_t* policy, double* out);
+int shyft_hip_ts_ice_packing_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                                  const int64_t* t_end, const int32_t* fx, const int64_t* qrow, const int64_t* qt,
+                                  const int64_t* window, const double* threshold, const int32_t* policy, double* out);
+/* shyft_hip_ts_ice_packing_recession replaces ice_packing_recession_ts::values() (core/time_series_dd.h:1313-1354).
+ * The series are the flows; ice [row[S]] is the indicator already sampled at the flow's points, ice_start / ice_end
+ * [S] the indicator's total period for ensure_overlap (:1358-1362, same text), alpha [S] and recession_minimum [S]
+ * the parameters. Without ice the flow's own f(t); with ice the recession from the last earlier point without ice
+ * (point 0 of the series when there is none); NaN on a non-finite indicator at the point or where the walk ends. */
+int shyft_hip_ts_ice_packing_recession(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                                       const int64_t* t_end, const int32_t* fx, const double* ice,
+                                       const int64_t* ice_start, const int64_t* ice_end, const double* alpha,
+                                       const double* recession_minimum, double* out);
+int shyft_hip_ts_ice_packing_recession_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                                            const int64_t* t_end, const int32_t* fx, const double* ice,
+                                            const int64_t* ice_start, const int64_t* ice_end, const double* alpha,
+                                            const double* recession_minimum, double* out);
+/* shyft_hip_ts_min_max_fill replaces qac_ts::value(i) without a replacement series (core/time_series_dd.cpp:1335-1376,
+ * qac_parameter core/time_series_dd.h:1456-1478): a finite value inside [min_x, max_x] (NaN = no limit) stays, any
+ * other becomes the line through the nearest valid neighbours, or NaN at the first and last point, with
+ * max_timespan == 0, without such neighbours, or when they lie more than max_timespan [S] (ticks) apart. */
+int shyft_hip_ts_min_max_fill(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                              const int64_t* t_end, const int32_t* fx, const double* min_x, const double* max_x,
+                              const int64_t* max_timespan, double* out);
+int shyft_hip_ts_min_max_fill_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                                   const int64_t* t_end, const int32_t* fx, const double* min_x, const double* max_x,
+                                   const int64_t* max_timespan, double* out);
+/* HIP-event milliseconds of the kernels of the last shyft_hip_ts_* device call on this device, copies excluded, and
+ * the number of such calls that launched so far. (No reference counterpart: measurement and test aid.) */
+double shyft_hip_tsprep_last_ms(int device);
+uint64_t shyft_hip_tsprep_calls(int device);
+
 size_t shyft_hip_number_of_catchments(const shyft_hip_region* h);
 int shyft_hip_catchment_ids(const shyft_hip_region* h, int64_t* cids);
 

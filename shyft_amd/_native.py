@@ -78,6 +78,17 @@ SIGNATURES = {
     "shyft_hip_resample_calls": (C.c_uint64, [C.c_int]),
     "shyft_hip_resample_set_path": (C.c_int, [C.c_int]),
     "shyft_hip_resample_last_path": (C.c_int, [C.c_int]),
+    "shyft_hip_ts_rating_curve": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 6),
+    "shyft_hip_ts_rating_curve_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t]
+                                       + [C.c_void_p] * 6),
+    "shyft_hip_ts_ice_packing": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 11),
+    "shyft_hip_ts_ice_packing_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 11),
+    "shyft_hip_ts_ice_packing_recession": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 11),
+    "shyft_hip_ts_ice_packing_recession_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 11),
+    "shyft_hip_ts_min_max_fill": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 9),
+    "shyft_hip_ts_min_max_fill_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 9),
+    "shyft_hip_tsprep_last_ms": (C.c_double, [C.c_int]),
+    "shyft_hip_tsprep_calls": (C.c_uint64, [C.c_int]),
     "shyft_hip_synthetic_elevation": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]),
     "shyft_hip_run_cells": (C.c_int, [_h, C.c_size_t, C.c_int, C.c_int]),
     "shyft_hip_run_cells_async": (C.c_int, [_h, C.c_int, C.c_int]),

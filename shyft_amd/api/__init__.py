@@ -25,6 +25,15 @@ from ._api import (  # noqa: F401  (re-exported names)
     KalmanParameter, KalmanState, KalmanFilter, no_utctime,
 )
 from . import _api
+from . import _tsprep
+from ._tsprep import (  # noqa: F401  (re-exported names)
+    RatingCurveSegment, RatingCurveFunction, RatingCurveParameters, IcePackingParameters,
+    IcePackingRecessionParameters, ice_packing_temperature_policy, max_utctime,
+)
+
+DISALLOW_MISSING = ice_packing_temperature_policy.DISALLOW_MISSING
+ALLOW_INITIAL_MISSING = ice_packing_temperature_policy.ALLOW_INITIAL_MISSING
+ALLOW_ANY_MISSING = ice_packing_temperature_policy.ALLOW_ANY_MISSING
 
 TimeAxis = TimeAxisFixedDeltaT
 ts_point_fx = point_interpretation_policy
@@ -180,6 +189,29 @@ class TimeSeries:
         the series on (accumulate_ts, time_series_dd.h:633-679), on the host."""
         return _resampled([self], ta, _RESAMPLE_ACCUMULATE, True)[0]
 
+    # observation preparation (api_time_series.cpp:651-653, 992-1253), one series on the host
+    def rating_curve(self, rc_param):
+        """the flow of a water-level series through the RatingCurveParameters (rating_curve_ts,
+        time_series.h:1548-1647); the level's point type"""
+        return _tsprep.rating_curve([self], rc_param, True)[0]
+
+    def ice_packing(self, ip_params, ipt_policy):
+        """the ice-packing indicator of a temperature series at its own points: 1.0 where the average over the
+        threshold window lies below the threshold temperature, 0.0 where not, NaN where the policy cannot tell
+        (ice_packing_ts, time_series.h:1685-1834); POINT_AVERAGE_VALUE"""
+        return _tsprep.ice_packing([self], ip_params, ipt_policy, True)[0]
+
+    def ice_packing_recession(self, ip_ts, ipr_params):
+        """this flow series with the recession curve wherever the indicator ip_ts says ice-packing
+        (ice_packing_recession_ts, time_series_dd.h:1220-1365); the flow's point type"""
+        return _tsprep.ice_packing_recession([self], [ip_ts], ipr_params, True)[0]
+
+    def min_max_check_linear_fill(self, v_min, v_max, dt_max=_tsprep.max_utctime):
+        """values that are NaN or outside [v_min, v_max] (NaN = no limit) replaced by the line through the nearest
+        valid neighbours, NaN when those are more than dt_max seconds apart (qac_ts, time_series_dd.cpp:1335-1376);
+        the source's point type"""
+        return _tsprep.min_max_check_linear_fill([self], v_min, v_max, dt_max, True)[0]
+
 
 # ---- average / integral / accumulate of a set of series in one call (region.resample) -------------------------------
 _RESAMPLE_AVERAGE, _RESAMPLE_INTEGRAL, _RESAMPLE_ACCUMULATE = 0, 1, 2  # region.RESAMPLE_*
@@ -314,6 +346,23 @@ class TsVector(_Vector):
         """the integral of every series from the start of a fixed_dt axis to each of its time points, in one device
         call, or with host=True on the host, bit-identical; a TsVector of POINT_INSTANT_VALUE series on ta."""
         return _resampled(self, ta, _RESAMPLE_ACCUMULATE, host)
+
+    # observation preparation: the TimeSeries methods of the same names for every series, each one device call
+    # (region.ts_*_csr), or with host=True on the host, bit-identical. A parameter is one object for all series or a
+    # sequence of len(self) objects.
+    def rating_curve(self, rc_param, *, host=False):
+        return _tsprep.rating_curve(self, rc_param, host)
+
+    def ice_packing(self, ip_params, ipt_policy, *, host=False):
+        return _tsprep.ice_packing(self, ip_params, ipt_policy, host)
+
+    def ice_packing_recession(self, ip_ts, ipr_params, *, host=False):
+        """ip_ts: a TsVector of indicators, one per flow series. Indicators made by ice_packing are first evaluated
+        at the flow's time points (a device call of their own), then the recession is one device call."""
+        return _tsprep.ice_packing_recession(self, ip_ts, ipr_params, host)
+
+    def min_max_check_linear_fill(self, v_min, v_max, dt_max=_tsprep.max_utctime, *, host=False):
+        return _tsprep.min_max_check_linear_fill(self, v_min, v_max, dt_max, host)
 
 
 class TsFactory:

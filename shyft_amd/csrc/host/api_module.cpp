@@ -254,6 +254,21 @@ PYBIND11_MODULE(_api, m) {
             return t;
         })
         .def_property_readonly("_t_end", [](const point_ts& s) { return to_s(s.t_end); })
+        // the series on the same points with other values (the results of the observation-preparation calls)
+        .def("_with_values", [](const point_ts& s, const std::vector<double>& v, ts_point_fx fx) {
+            if (v.size() != s.size()) throw std::runtime_error("point_ts: values and time-axis differ in size");
+            point_ts r(s);
+            r.v = v;
+            r.fx = fx;
+            return r;
+        })
+        // f(t) at times in microseconds, and the total period in microseconds
+        .def("_sample_us", [](const point_ts& s, const std::vector<int64_t>& t) {
+            py::array_t<double> r(py::ssize_t(t.size()));
+            for (size_t i = 0; i < t.size(); ++i) r.mutable_data()[i] = s(t[i]);
+            return r;
+        })
+        .def("_total_period_us", [](const point_ts& s) { auto p = s.total_period(); return std::make_pair(p.start, p.end); })
         .def("average", [](const point_ts& s, const fixed_dt& ta) {
             auto v = average_values(s, ta);
             return py::array_t<double>(v.size(), v.data());

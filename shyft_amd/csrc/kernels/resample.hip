@@ -29,7 +29,7 @@
 //
 // Index safety. The host checks before the launch that row[0] == 0 and row is non-decreasing, so a series' points
 // are t[row[s] .. row[s+1]) inside the uploaded row[S] points, and that its times increase strictly and t_end lies
-// after the last. rs_area reads point k only with k < n: the start index is at most n - 1, every read is followed
+// after the last. rs_area (device/ts_area.h, shared with kernels/tsprep.hip) reads point k only with k < n: the start index is at most n - 1, every read is followed
 // by the test `k == n` which ends the walk, and the one place where the reference reads without that test (a
 // one-point series whose point lies inside a period that starts before it, where the reference throws from
 // point_dt::time) is refused by the host check and, should it reach the device, ends the walk with NaN. A series
@@ -48,6 +48,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../device/ts_area.h"
 #include "../host/time_series.hpp"
 #include "../include_internal/region_impl.h"
 
@@ -60,7 +61,6 @@ constexpr int RS_TILE_S = 16;   // series per TILED workgroup tile: 128-byte run
 constexpr int RS_TILE_T = 64;   // intervals per tile: one per lane
 constexpr int RS_TILE_LD = RS_TILE_S + 1;
 constexpr int RS_SCAN_ROWS = 8;  // rows the ACCUMULATE scan loads ahead of its adds
-constexpr uint64_t RS_EXPO = 0x7ff0000000000000ull;
 
 struct rs_args {
     int mode;
@@ -73,102 +73,6 @@ struct rs_args {
     int64_t ta_t0, ta_dt;
     double* out;
 };
-
-__device__ inline double rs_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ inline bool rs_finite(double x) { return ((uint64_t)__double_as_longlong(x) & RS_EXPO) != RS_EXPO; }
-__device__ inline double rs_seconds(int64_t dt) { return double(dt) / 1e6; }
-__device__ inline int64_t rs_max(int64_t a, int64_t b) { return a > b ? a : b; }
-__device__ inline int64_t rs_min(int64_t a, int64_t b) { return a < b ? a : b; }
-
-// accumulate_value(source, [ps, pe), ., tsum, linear, strict_linear_between = true) over the n > 0 points t, v of
-// one series (host/time_series.hpp accumulate_value, statement by statement); tsum == 0 gives NaN
-__device__ inline double rs_area(const int64_t* __restrict__ t, const double* __restrict__ v, int64_t n, int64_t t_end,
-                                 int64_t ps, int64_t pe, bool linear, int64_t& tsum) {
-    const bool extrapolate_flat = !linear;
-    tsum = 0;
-    // open_range_index_of(ps): -1 before the first point, n - 1 from the last point on
-    int64_t i;
-    if (ps >= t_end) {
-        i = n - 1;
-    } else if (ps < t[0]) {
-        i = -1;
-    } else if (ps >= t[n - 1]) {
-        i = n - 1;
-    } else {  // upper_bound - 1; t[0] <= ps < t[n-1]
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t m = lo + ((hi - lo) >> 1);
-            if (t[m] <= ps) lo = m + 1;
-            else hi = m;
-        }
-        i = lo - 1;
-    }
-    int64_t lt = 0;
-    double lv = rs_nan();
-    bool l_finite = false;
-    if (i < 0) {
-        i = 0;
-        lt = t[i];
-        lv = v[i];
-        ++i;
-        l_finite = rs_finite(lv);
-        if (!(lt >= ps && lt < pe)) return rs_nan();
-        if (i == n) return rs_nan();  // the reference throws here; the host check refuses it before the launch
-    }
-    double area = 0.0;
-    while (true) {
-        if (!l_finite) {
-            lt = t[i];
-            lv = v[i];
-            ++i;
-            l_finite = rs_finite(lv);
-            if (i == n) {
-                if (l_finite && lt < pe) {
-                    if (extrapolate_flat) {
-                        const int64_t dt = pe - rs_max(ps, lt);
-                        tsum += dt;
-                        area += rs_seconds(dt) * lv;
-                    }
-                }
-                break;
-            }
-            if (lt >= pe) break;
-        } else {
-            const int64_t rt = t[i];
-            const double rv = v[i];
-            ++i;
-            const bool r_finite = rs_finite(rv);
-            const int64_t px_start = rs_max(lt, ps), px_end = rs_min(rt, pe);
-            int64_t dt = px_end - px_start;
-            if (linear && r_finite) {
-                const double a = (rv - lv) / rs_seconds(rt - lt);
-                const double b = rv - a * rs_seconds(rt);
-                area += rs_seconds(dt) * (0.5 * a * rs_seconds(px_start + px_end) + b);
-                tsum += dt;
-            } else {
-                if (extrapolate_flat) {
-                    area += lv * rs_seconds(dt);
-                    tsum += dt;
-                }
-            }
-            if (i == n) {
-                if (r_finite && rt < pe) {
-                    if (extrapolate_flat) {
-                        dt = pe - rt;
-                        tsum += dt;
-                        area += rs_seconds(dt) * rv;
-                    }
-                }
-                break;
-            }
-            if (rt >= pe) break;
-            l_finite = r_finite;
-            lt = rt;
-            lv = rv;
-        }
-    }
-    return tsum ? area : rs_nan();
-}
 
 // one (series, interval) job; s < S, i < T
 __device__ inline double rs_job(const rs_args& a, size_t s, size_t i) {

@@ -605,3 +605,125 @@ def resample_set_path(path: int) -> None:
 def resample_last_path(device: int = -1) -> int:
     """RESAMPLE_PATH_DIRECT or RESAMPLE_PATH_TILED: the launch shape of the last resample on the device."""
     return int(lib().shyft_hip_resample_last_path(device))
+
+
+# ---- observation preparation: rating curve, ice packing, recession, min-max fill (kernels/tsprep.hip) ------------------
+ICE_DISALLOW_MISSING, ICE_ALLOW_INITIAL_MISSING, ICE_ALLOW_ANY_MISSING = 0, 1, 2
+
+
+def _tsprep_series(what, row, t, v, t_end, fx):
+    row = np.ascontiguousarray(row, dtype=np.int64).reshape(-1)
+    t = np.ascontiguousarray(t, dtype=np.int64).reshape(-1)
+    v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+    t_end = np.ascontiguousarray(t_end, dtype=np.int64).reshape(-1)
+    fx = np.ascontiguousarray(fx, dtype=np.int32).reshape(-1)
+    S = row.shape[0] - 1
+    if S < 0 or t_end.shape[0] != S or fx.shape[0] != S:
+        raise ValueError(f"{what}: row must have one entry more than t_end and fx")
+    if t.shape[0] != v.shape[0] or (S and (row[0] != 0 or row[-1] != t.shape[0])):
+        raise ValueError(f"{what}: row must run from 0 to the number of points")
+    return S, row, t, v, t_end, fx
+
+
+def _per_series(what, name, x, S, dtype):
+    """one value for all series, or one per series"""
+    a = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+    if a.shape[0] == 1 and S != 1:
+        a = np.repeat(a, S)
+    if a.shape[0] != S:
+        raise ValueError(f"{what}: {name} must hold one value or one per series")
+    return np.ascontiguousarray(a)
+
+
+def ts_rating_curve_csr(row, t, v, t_end, fx, pack_row, curve_t, curve_row, seg, pack_of=0, device: int = -1,
+                        host: bool = False) -> np.ndarray:
+    """Water levels to flow through rating-curve parameter packs, one value per point in CSR order
+    (shyft_hip_ts_rating_curve; rating_curve_parameters::flow, core/time_series.h:1493-1506). The S level series are in
+    the CSR form of resample_csr. The packs are a three-level CSR: pack_row [P+1] -> curve_t [C] curve start times
+    (int64 microseconds) -> curve_row [C+1] -> seg [G][4] = lower, a, b, c; pack_of names the pack of each series (one
+    value for all, or [S]). host=True runs the host restatement, which the device is bit-identical to."""
+    S, row, t, v, t_end, fx = _tsprep_series("ts_rating_curve", row, t, v, t_end, fx)
+    pack_row = np.ascontiguousarray(pack_row, dtype=np.int64).reshape(-1)
+    curve_t = np.ascontiguousarray(curve_t, dtype=np.int64).reshape(-1)
+    curve_row = np.ascontiguousarray(curve_row, dtype=np.int64).reshape(-1)
+    seg = np.ascontiguousarray(seg, dtype=np.float64).reshape(-1, 4)
+    pack_of = _per_series("ts_rating_curve", "pack_of", pack_of, S, np.int64)
+    P = pack_row.shape[0] - 1
+    if P < 0 or (P and (pack_row[0] != 0 or pack_row[-1] != curve_t.shape[0])) or curve_row.shape[0] != curve_t.shape[0] + 1 \
+            or curve_row[0] != 0 or curve_row[-1] != seg.shape[0]:
+        raise ValueError("ts_rating_curve: pack_row, curve_t, curve_row and seg do not form a CSR")
+    out = np.empty(t.shape[0], dtype=np.float64)
+    fn = lib().shyft_hip_ts_rating_curve_host if host else lib().shyft_hip_ts_rating_curve
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), P, _ptr(pack_row), _ptr(curve_t),
+             _ptr(curve_row), _ptr(seg), _ptr(pack_of), _ptr(out)), None)
+    return out
+
+
+def ts_ice_packing_csr(row, t, v, t_end, fx, qrow, qt, window, threshold, policy=ICE_DISALLOW_MISSING, device: int = -1,
+                       host: bool = False) -> np.ndarray:
+    """The ice-packing indicator of S temperature series at query times of their own CSR (qrow [S+1], qt int64
+    microseconds), one value per query (shyft_hip_ts_ice_packing; ice_packing_ts::detect_ice_packing,
+    core/time_series.h:1808-1831): 1.0 when the average over [t - window, t) is below the threshold, 0.0 when not, NaN
+    when the policy cannot tell. window (int64 microseconds), threshold and policy (ICE_*) are one value for all
+    series or [S]. Pass qrow=row, qt=t for the series' own points."""
+    S, row, t, v, t_end, fx = _tsprep_series("ts_ice_packing", row, t, v, t_end, fx)
+    qrow = np.ascontiguousarray(qrow, dtype=np.int64).reshape(-1)
+    qt = np.ascontiguousarray(qt, dtype=np.int64).reshape(-1)
+    if qrow.shape[0] != S + 1 or (S and (qrow[0] != 0 or qrow[-1] != qt.shape[0])):
+        raise ValueError("ts_ice_packing: qrow must run from 0 to the number of queries")
+    window = _per_series("ts_ice_packing", "window", window, S, np.int64)
+    threshold = _per_series("ts_ice_packing", "threshold", threshold, S, np.float64)
+    policy = _per_series("ts_ice_packing", "policy", policy, S, np.int32)
+    out = np.empty(qt.shape[0], dtype=np.float64)
+    fn = lib().shyft_hip_ts_ice_packing_host if host else lib().shyft_hip_ts_ice_packing
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), _ptr(qrow), _ptr(qt), _ptr(window),
+             _ptr(threshold), _ptr(policy), _ptr(out)), None)
+    return out
+
+
+def ts_ice_packing_recession_csr(row, t, v, t_end, fx, ice, ice_start, ice_end, alpha, recession_minimum,
+                                 device: int = -1, host: bool = False) -> np.ndarray:
+    """S flow series with the recession curve wherever the indicator `ice` (one value per flow point, already sampled
+    at the flow's points) says ice-packing, one value per point (shyft_hip_ts_ice_packing_recession;
+    ice_packing_recession_ts::evaluate, core/time_series_dd.h:1323-1354). ice_start / ice_end [S] are the indicator's
+    total period (the flow's must lie inside); alpha [1/s] and recession_minimum are one value for all or [S]."""
+    S, row, t, v, t_end, fx = _tsprep_series("ts_ice_packing_recession", row, t, v, t_end, fx)
+    ice = np.ascontiguousarray(ice, dtype=np.float64).reshape(-1)
+    if ice.shape[0] != t.shape[0]:
+        raise ValueError("ts_ice_packing_recession: ice must hold one value per flow point")
+    ice_start = _per_series("ts_ice_packing_recession", "ice_start", ice_start, S, np.int64)
+    ice_end = _per_series("ts_ice_packing_recession", "ice_end", ice_end, S, np.int64)
+    alpha = _per_series("ts_ice_packing_recession", "alpha", alpha, S, np.float64)
+    qmin = _per_series("ts_ice_packing_recession", "recession_minimum", recession_minimum, S, np.float64)
+    out = np.empty(t.shape[0], dtype=np.float64)
+    fn = lib().shyft_hip_ts_ice_packing_recession_host if host else lib().shyft_hip_ts_ice_packing_recession
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), _ptr(ice), _ptr(ice_start), _ptr(ice_end),
+             _ptr(alpha), _ptr(qmin), _ptr(out)), None)
+    return out
+
+
+def ts_min_max_fill_csr(row, t, v, t_end, fx, min_x, max_x, max_timespan, device: int = -1,
+                        host: bool = False) -> np.ndarray:
+    """S series with every value that is not finite or lies outside [min_x, max_x] (NaN = no limit) replaced by the
+    line through its nearest valid neighbours, or NaN when they are missing or more than max_timespan (int64
+    microseconds) apart, one value per point (shyft_hip_ts_min_max_fill; qac_ts::value,
+    core/time_series_dd.cpp:1335-1376). The three parameters are one value for all series or [S]."""
+    S, row, t, v, t_end, fx = _tsprep_series("ts_min_max_fill", row, t, v, t_end, fx)
+    min_x = _per_series("ts_min_max_fill", "min_x", min_x, S, np.float64)
+    max_x = _per_series("ts_min_max_fill", "max_x", max_x, S, np.float64)
+    span = _per_series("ts_min_max_fill", "max_timespan", max_timespan, S, np.int64)
+    out = np.empty(t.shape[0], dtype=np.float64)
+    fn = lib().shyft_hip_ts_min_max_fill_host if host else lib().shyft_hip_ts_min_max_fill
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), _ptr(min_x), _ptr(max_x), _ptr(span),
+             _ptr(out)), None)
+    return out
+
+
+def tsprep_last_ms(device: int = -1) -> float:
+    """HIP-event milliseconds of the kernels of the last ts_*_csr device call on the device, copies excluded."""
+    return float(lib().shyft_hip_tsprep_last_ms(device))
+
+
+def tsprep_calls(device: int = -1) -> int:
+    """The number of ts_*_csr device calls that launched on the device so far."""
+    return int(lib().shyft_hip_tsprep_calls(device))
