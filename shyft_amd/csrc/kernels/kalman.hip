@@ -18,17 +18,14 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <limits>
-#include <memory>
 #include <stdexcept>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../../detmath/detmath.h"
-#include "../include_internal/region_impl.h"
+#include "../include_internal/device_call.h"
 
 using namespace shyft_hip_impl;
 
@@ -256,14 +253,9 @@ bool kalman_prepare(const char* who, int n, size_t M, size_t T, const double* bi
     return false;
 }
 
-constexpr int KALMAN_MAX_DEVICES = 64;
-std::atomic<double> g_kalman_last_ms[KALMAN_MAX_DEVICES];
-
-template <class T>
-void upload(dbuf<T>& d, const T* src, size_t count, hipStream_t s) {
-    d.alloc(count);
-    if (count) hip_check(hipMemcpyAsync(d.p, src, count * sizeof(T), hipMemcpyHostToDevice, s), "kalman upload");
-}
+per_device<double> g_kalman_last_ms;
+constexpr const char* KALMAN_UPLOAD = "kalman upload";
+constexpr const char* KALMAN_DOWNLOAD = "kalman download";
 
 }  // namespace
 
@@ -278,30 +270,16 @@ int shyft_hip_kalman_run(int device, int n, size_t M, size_t T, const double* bi
             return 0;
         if (M * size_t(KALMAN_MAX_N) / KALMAN_BLOCK + 1 > size_t(std::numeric_limits<int>::max()))
             throw std::runtime_error("kalman: too many points for one launch");
-        if (device >= 0) hip_check(hipSetDevice(device), "hipSetDevice");
-        int dev = 0;
-        hip_check(hipGetDevice(&dev), "hipGetDevice");
-        hipStream_t s = nullptr;
-        hip_check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
-        std::unique_ptr<std::remove_pointer<hipStream_t>::type, void (*)(hipStream_t)> stream(
-            s, [](hipStream_t q) { (void)hipStreamDestroy(q); });
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        hip_check(hipEventCreate(&e0), "hipEventCreate");
-        std::unique_ptr<std::remove_pointer<hipEvent_t>::type, void (*)(hipEvent_t)> ev0(
-            e0, [](hipEvent_t q) { (void)hipEventDestroy(q); });
-        hip_check(hipEventCreate(&e1), "hipEventCreate");
-        std::unique_ptr<std::remove_pointer<hipEvent_t>::type, void (*)(hipEvent_t)> ev1(
-            e1, [](hipEvent_t q) { (void)hipEventDestroy(q); });
-
+        device_call c(device);
         const size_t nn = size_t(n) * n;
         dbuf<double> d_bias, d_w, d_x, d_k, d_P, d_out, d_sec;
         dbuf<int32_t> d_fold, d_pb, d_pi;
-        upload(d_bias, bias, T * M, s);
-        upload(d_fold, fold, T, s);
-        upload(d_w, w, size_t(n / 2 + 1), s);
-        upload(d_x, x, size_t(n) * M, s);
-        upload(d_k, k, size_t(n) * M, s);
-        upload(d_P, P, nn * M, s);
+        c.upload(d_bias, bias, T * M, KALMAN_UPLOAD);
+        c.upload(d_fold, fold, T, KALMAN_UPLOAD);
+        c.upload(d_w, w, size_t(n / 2 + 1), KALMAN_UPLOAD);
+        c.upload(d_x, x, size_t(n) * M, KALMAN_UPLOAD);
+        c.upload(d_k, k, size_t(n) * M, KALMAN_UPLOAD);
+        c.upload(d_P, P, nn * M, KALMAN_UPLOAD);
         kalman_dev_args a{};
         a.n = n;
         a.M = M;
@@ -318,26 +296,23 @@ int shyft_hip_kalman_run(int device, int n, size_t M, size_t T, const double* bi
         if (out) {
             const size_t np = size_t(piece_begin[T]);
             d_out.alloc(T * M);
-            upload(d_pb, piece_begin, T + 1, s);
-            upload(d_pi, piece_ix, np, s);
-            upload(d_sec, piece_seconds, np, s);
+            c.upload(d_pb, piece_begin, T + 1, KALMAN_UPLOAD);
+            c.upload(d_pi, piece_ix, np, KALMAN_UPLOAD);
+            c.upload(d_sec, piece_seconds, np, KALMAN_UPLOAD);
             a.out = d_out.p;
             a.save_every = save_every;
             a.piece_begin = d_pb.p;
             a.piece_ix = d_pi.p;
             a.piece_seconds = d_sec.p;
         }
-        hip_check(hipEventRecord(e0, s), "hipEventRecord");
-        hip_check(launch_kalman(a, s), "kalman_run");
-        hip_check(hipEventRecord(e1, s), "hipEventRecord");
-        hip_check(hipMemcpyAsync(x, d_x.p, size_t(n) * M * sizeof(double), hipMemcpyDeviceToHost, s), "kalman download");
-        hip_check(hipMemcpyAsync(k, d_k.p, size_t(n) * M * sizeof(double), hipMemcpyDeviceToHost, s), "kalman download");
-        hip_check(hipMemcpyAsync(P, d_P.p, nn * M * sizeof(double), hipMemcpyDeviceToHost, s), "kalman download");
-        if (out) hip_check(hipMemcpyAsync(out, d_out.p, T * M * sizeof(double), hipMemcpyDeviceToHost, s), "kalman download");
-        hip_check(hipStreamSynchronize(s), "kalman_run");
-        float ms = 0.f;
-        hip_check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-        if (dev >= 0 && dev < KALMAN_MAX_DEVICES) g_kalman_last_ms[dev].store(double(ms));
+        c.begin();
+        hip_check(launch_kalman(a, c.s), "kalman_run");
+        c.end();
+        c.download(x, d_x.p, size_t(n) * M, KALMAN_DOWNLOAD);
+        c.download(k, d_k.p, size_t(n) * M, KALMAN_DOWNLOAD);
+        c.download(P, d_P.p, nn * M, KALMAN_DOWNLOAD);
+        if (out) c.download(out, d_out.p, T * M, KALMAN_DOWNLOAD);
+        g_kalman_last_ms.store(c.dev, c.finish("kalman_run"));
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -389,9 +364,6 @@ int shyft_hip_kalman_initial_state(int n, double covariance_init, double hourly_
     return 0;
 }
 
-double shyft_hip_kalman_last_ms(int device) {
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return 0.0;
-    return device >= 0 && device < KALMAN_MAX_DEVICES ? g_kalman_last_ms[device].load() : 0.0;
-}
+double shyft_hip_kalman_last_ms(int device) { return g_kalman_last_ms.load(device, 0.0); }
 
 }  // extern "C"

@@ -26,25 +26,11 @@
 #include <vector>
 
 #include "../../../detmath/detmath.h"
-#include "../include_internal/kernels.h"
+#include "../include_internal/region_impl.h"
+
+using shyft_hip_impl::hip_check;
 
 namespace {
-
-void check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string("ordinary kriging ") + what + ": " + hipGetErrorString(e));
-}
-
-template <class T>
-struct devbuf {
-    T* p = nullptr;
-    devbuf() = default;
-    devbuf(const devbuf&) = delete;
-    devbuf& operator=(const devbuf&) = delete;
-    ~devbuf() {
-        if (p) (void)hipFree(p);
-    }
-    void alloc(size_t count) { check(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)), "hipMalloc"); }
-};
 
 // cov(src, dst) of the contract: h2 left to right as geo_point::zscaled_distance2 writes it (core/geo_point.h:49-58),
 // EXPONENTIAL c exp(h k1), GAUSSIAN c exp(h2 k2) (core/kriging.h:26-64), k = k1 or k2 made once on the host
@@ -245,34 +231,36 @@ void ok_run(const ok_args& a, hipStream_t stream) {
     // a pass stays below 2^30 destinations: the kernels index them with int
     const size_t blk = std::min({m, a.dst_block ? a.dst_block : ok_default_dst_block(), size_t(1) << 30});
 
-    devbuf<double> d_src, d_left, d_obs, d_BW;
+    // every count below is > 0: n >= 2 (check_limits), ldw and ldo >= OK_RT, 1 <= blk <= m
+    dbuf<double> d_src, d_left, d_obs, d_BW;
     d_src.alloc(3 * n);
     d_left.alloc(left.size());
     d_obs.alloc(n * ldo);
     d_BW.alloc((2 * n + 1) * blk);  // B (N rows) then W (n rows): within 2 (n+1) dst_block doubles
     double* d_B = d_BW.p;
     double* d_W = d_BW.p + N * blk;
-    check(hipMemcpyAsync(d_src.p, a.src_xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, stream), "upload");
-    check(hipMemcpyAsync(d_left.p, left.data(), left.size() * sizeof(double), hipMemcpyHostToDevice, stream), "upload");
+    const char* up = "ordinary kriging upload";
+    hip_check(hipMemcpyAsync(d_src.p, a.src_xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, stream), up);
+    hip_check(hipMemcpyAsync(d_left.p, left.data(), left.size() * sizeof(double), hipMemcpyHostToDevice, stream), up);
     std::vector<double> obs(n * ldo);
     for (size_t t0 = 0; t0 < T; t0 += step_block) {
         const size_t tb = std::min(step_block, T - t0);
         std::fill(obs.begin(), obs.end(), 0.0);
         for (size_t t = 0; t < tb; ++t)
             for (size_t s = 0; s < n; ++s) obs[s * ldo + t] = a.src_values[(t0 + t) * n + s];
-        check(hipMemcpyAsync(d_obs.p, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice, stream), "upload");
+        hip_check(hipMemcpyAsync(d_obs.p, obs.data(), obs.size() * sizeof(double), hipMemcpyHostToDevice, stream), up);
         for (size_t d0 = 0; d0 < m; d0 += blk) {
             const size_t mb = std::min(blk, m - d0);
-            check(launch_ok_cov(d_src.p, int(n), a.d_dst_xyz + 3 * d0, int(mb), a.c, ok_k(a), a.z_scale, a.cov_type == 0,
-                                d_B, mb, stream),
-                  "covariance kernel");
-            check(launch_ok_product(d_left.p, int(ldw), int(n), d_B, mb, int(N), int(mb), d_W, mb, stream),
-                  "weights kernel");
-            check(launch_ok_product(d_obs.p, int(ldo), int(tb), d_W, mb, int(n), int(mb), a.d_out + t0 * a.ld_out + d0,
-                                    a.ld_out, stream),
-                  "values kernel");
+            hip_check(launch_ok_cov(d_src.p, int(n), a.d_dst_xyz + 3 * d0, int(mb), a.c, ok_k(a), a.z_scale,
+                                    a.cov_type == 0, d_B, mb, stream),
+                      "ordinary kriging covariance kernel");
+            hip_check(launch_ok_product(d_left.p, int(ldw), int(n), d_B, mb, int(N), int(mb), d_W, mb, stream),
+                      "ordinary kriging weights kernel");
+            hip_check(launch_ok_product(d_obs.p, int(ldo), int(tb), d_W, mb, int(n), int(mb),
+                                        a.d_out + t0 * a.ld_out + d0, a.ld_out, stream),
+                      "ordinary kriging values kernel");
         }
-        check(hipStreamSynchronize(stream), "sync");  // obs is refilled for the next block of steps
+        hip_check(hipStreamSynchronize(stream), "ordinary kriging sync");  // obs is refilled for the next block of steps
     }
 }
 

@@ -32,18 +32,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <memory>
 #include <stdexcept>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../host/qm.hpp"
-#include "../include_internal/region_impl.h"
+#include "../include_internal/device_call.h"
 
 using namespace shyft_hip_impl;
 
@@ -275,15 +272,9 @@ bool qm_prepare(const char* who, size_t B, size_t T, size_t F, size_t P, const d
     return false;
 }
 
-constexpr int QM_MAX_DEVICES = 64;
-std::atomic<double> g_qm_last_ms[QM_MAX_DEVICES];
-std::atomic<int> g_qm_last_path[QM_MAX_DEVICES];
-
-template <class T>
-void qm_upload(dbuf<T>& d, const T* src, size_t count, hipStream_t s) {
-    d.alloc(count);
-    if (count) hip_check(hipMemcpyAsync(d.p, src, count * sizeof(T), hipMemcpyHostToDevice, s), "quantile_map upload");
-}
+per_device<double> g_qm_last_ms;
+per_device<int> g_qm_last_path;
+constexpr const char* QM_UPLOAD = "quantile_map upload";
 
 }  // namespace
 
@@ -300,28 +291,14 @@ int shyft_hip_quantile_map(int device, size_t B, size_t T, size_t F, size_t P, c
         }
         if (B * T > size_t(std::numeric_limits<int>::max()))
             throw std::runtime_error("quantile_map: too many (problem, step) jobs for one launch");
-        if (device >= 0) hip_check(hipSetDevice(device), "hipSetDevice");
-        int dev = 0;
-        hip_check(hipGetDevice(&dev), "hipGetDevice");
-        hipStream_t s = nullptr;
-        hip_check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
-        std::unique_ptr<std::remove_pointer<hipStream_t>::type, void (*)(hipStream_t)> stream(
-            s, [](hipStream_t q) { (void)hipStreamDestroy(q); });
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        hip_check(hipEventCreate(&e0), "hipEventCreate");
-        std::unique_ptr<std::remove_pointer<hipEvent_t>::type, void (*)(hipEvent_t)> ev0(
-            e0, [](hipEvent_t q) { (void)hipEventDestroy(q); });
-        hip_check(hipEventCreate(&e1), "hipEventCreate");
-        std::unique_ptr<std::remove_pointer<hipEvent_t>::type, void (*)(hipEvent_t)> ev1(
-            e1, [](hipEvent_t q) { (void)hipEventDestroy(q); });
-
+        device_call c(device);
         dbuf<double> d_fc, d_w, d_pri, d_iw, d_out;
         dbuf<int32_t> d_mode;
-        qm_upload(d_fc, fc, B * T * F, s);
-        qm_upload(d_w, w, F, s);
-        qm_upload(d_pri, pri, B * T * P, s);
-        qm_upload(d_mode, mode, T, s);
-        qm_upload(d_iw, interp_weight, T, s);
+        c.upload(d_fc, fc, B * T * F, QM_UPLOAD);
+        c.upload(d_w, w, F, QM_UPLOAD);
+        c.upload(d_pri, pri, B * T * P, QM_UPLOAD);
+        c.upload(d_mode, mode, T, QM_UPLOAD);
+        c.upload(d_iw, interp_weight, T, QM_UPLOAD);
         d_out.alloc(B * T * P);
         qm_args a{};
         a.jobs = B * T;
@@ -341,24 +318,18 @@ int shyft_hip_quantile_map(int device, size_t B, size_t T, size_t F, size_t P, c
         a.out = d_out.p;
         const bool wave = a.SF <= 64 && a.SP <= 64;
         const size_t job_bytes = qm_job_bytes(a.SF, a.SP);  // <= 48 KiB + 16 at the cap
-        hip_check(hipEventRecord(e0, s), "hipEventRecord");
+        c.begin();
         if (wave) {
             const unsigned grid = unsigned((a.jobs + QM_WAVE_JOBS - 1) / QM_WAVE_JOBS);
-            hipLaunchKernelGGL(qm_kernel<true>, dim3(grid), dim3(QM_BLOCK), QM_WAVE_JOBS * job_bytes, s, a);
+            hipLaunchKernelGGL(qm_kernel<true>, dim3(grid), dim3(QM_BLOCK), QM_WAVE_JOBS * job_bytes, c.s, a);
         } else {
-            hipLaunchKernelGGL(qm_kernel<false>, dim3(unsigned(a.jobs)), dim3(QM_BLOCK), job_bytes, s, a);
+            hipLaunchKernelGGL(qm_kernel<false>, dim3(unsigned(a.jobs)), dim3(QM_BLOCK), job_bytes, c.s, a);
         }
         hip_check(hipGetLastError(), "quantile_map");
-        hip_check(hipEventRecord(e1, s), "hipEventRecord");
-        hip_check(hipMemcpyAsync(out, d_out.p, B * T * P * sizeof(double), hipMemcpyDeviceToHost, s),
-                  "quantile_map download");
-        hip_check(hipStreamSynchronize(s), "quantile_map");
-        float ms = 0.f;
-        hip_check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-        if (dev >= 0 && dev < QM_MAX_DEVICES) {
-            g_qm_last_ms[dev].store(double(ms));
-            g_qm_last_path[dev].store(wave ? SHYFT_HIP_QM_PATH_WAVE : SHYFT_HIP_QM_PATH_GROUP);
-        }
+        c.end();
+        c.download(out, d_out.p, B * T * P, "quantile_map download");
+        g_qm_last_ms.store(c.dev, c.finish("quantile_map"));
+        g_qm_last_path.store(c.dev, wave ? SHYFT_HIP_QM_PATH_WAVE : SHYFT_HIP_QM_PATH_GROUP);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -382,14 +353,8 @@ int shyft_hip_quantile_map_host(size_t B, size_t T, size_t F, size_t P, const do
     }
 }
 
-int shyft_hip_quantile_map_last_path(int device) {
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return SHYFT_HIP_QM_PATH_NONE;
-    return device >= 0 && device < QM_MAX_DEVICES ? g_qm_last_path[device].load() : SHYFT_HIP_QM_PATH_NONE;
-}
+int shyft_hip_quantile_map_last_path(int device) { return g_qm_last_path.load(device, SHYFT_HIP_QM_PATH_NONE); }
 
-double shyft_hip_quantile_map_last_ms(int device) {
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return 0.0;
-    return device >= 0 && device < QM_MAX_DEVICES ? g_qm_last_ms[device].load() : 0.0;
-}
+double shyft_hip_quantile_map_last_ms(int device) { return g_qm_last_ms.load(device, 0.0); }
 
 }  // extern "C"

@@ -42,15 +42,14 @@
 #include <atomic>
 #include <cmath>
 #include <limits>
-#include <memory>
 #include <stdexcept>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../device/ts_area.h"
 #include "../host/time_series.hpp"
-#include "../include_internal/region_impl.h"
+#include "../include_internal/device_call.h"
+#include "../include_internal/series_args.h"
 
 using namespace shyft_hip_impl;
 
@@ -151,8 +150,9 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_scan_kernel(size_t S, size_
     }
 }
 
-// Argument checks shared by the device and the host entry, with the texts of host/time_series.hpp point_ts (core/time_axis.h:271-293);
-// true when there is nothing to do.
+// Argument checks shared by the device and the host entry: the axis and the batch here, the series through
+// include_internal/series_args.h; true when there is nothing to do. The axis' share of the quarter-range test and the
+// one-point rule keep their place after the checks of their series and before those of the next one.
 bool rs_prepare(const char* who, int mode, size_t S, const int64_t* row, const int64_t* t, const double* v,
                 const int64_t* t_end, const int32_t* fx, int64_t ta_t0, int64_t ta_dt, size_t T, const double* out) {
     if (mode != SHYFT_HIP_RESAMPLE_AVERAGE && mode != SHYFT_HIP_RESAMPLE_INTEGRAL && mode != SHYFT_HIP_RESAMPLE_ACCUMULATE)
@@ -163,22 +163,15 @@ bool rs_prepare(const char* who, int mode, size_t S, const int64_t* row, const i
     if (T > size_t(i64max / ta_dt) || ta_t0 > i64max - int64_t(T) * ta_dt)
         throw std::runtime_error("resample: the time-axis does not fit in 64-bit microseconds");
     if (T > std::numeric_limits<size_t>::max() / sizeof(double) / S) throw std::runtime_error("resample: the batch is too large");
-    if (!row || !t_end || !fx || !out) throw std::runtime_error(std::string(who) + ": null argument");
-    if (row[0] != 0) throw std::runtime_error("resample: row[0] must be 0");
-    for (size_t s = 0; s < S; ++s)
-        if (row[s + 1] < row[s]) throw std::runtime_error("resample: row must not decrease");
-    if (row[S] > 0 && (!t || !v)) throw std::runtime_error(std::string(who) + ": null argument");
+    if (!out) throw std::runtime_error(std::string(who) + ": null argument");
+    check_point_series_rows(who, "resample", S, row, t, v, t_end, fx);
     const int64_t ta_end = ta_t0 + int64_t(T) * ta_dt;
     for (size_t s = 0; s < S; ++s) {
-        if (fx[s] != int32_t(shyft_hip::host::POINT_INSTANT_VALUE) && fx[s] != int32_t(shyft_hip::host::POINT_AVERAGE_VALUE))
-            throw std::runtime_error("resample: fx must be POINT_INSTANT_VALUE or POINT_AVERAGE_VALUE");
+        check_point_series_at("resample", s, row, t, t_end, fx);
         const int64_t b = row[s], e = row[s + 1];
         if (b == e) continue;
-        for (int64_t k = b + 1; k < e; ++k)
-            if (!(t[k - 1] < t[k])) throw std::runtime_error("time_axis::point_dt() needs time-points in increasing order");
-        if (!(t_end[s] > t[e - 1])) throw std::runtime_error("time_axis::point_dt() illegal end-of-axis");
         // the sums to_seconds(px.start + px.end) and p.end - p.start stay inside int64
-        if (t[b] < i64min / 4 || t_end[s] > i64max / 4 || ta_t0 < i64min / 4 || ta_end > i64max / 4)
+        if (ta_t0 < i64min / 4 || ta_end > i64max / 4)
             throw std::runtime_error("resample: times beyond a quarter of the 64-bit range are not supported");
         if (e - b == 1) {
             // accumulate_value reads point 1 of a one-point series when the point lies inside a period that starts
@@ -192,17 +185,11 @@ bool rs_prepare(const char* who, int mode, size_t S, const int64_t* row, const i
     return false;
 }
 
-constexpr int RS_MAX_DEVICES = 64;
-std::atomic<double> g_rs_last_ms[RS_MAX_DEVICES];
-std::atomic<uint64_t> g_rs_calls[RS_MAX_DEVICES];
-std::atomic<int> g_rs_last_path[RS_MAX_DEVICES];
+per_device<double> g_rs_last_ms;
+per_device<uint64_t> g_rs_calls;
+per_device<int> g_rs_last_path;
 std::atomic<int> g_rs_path{SHYFT_HIP_RESAMPLE_PATH_AUTO};
-
-template <class T>
-void rs_upload(dbuf<T>& d, const T* src, size_t count, hipStream_t s) {
-    d.alloc(count);
-    if (count) hip_check(hipMemcpyAsync(d.p, src, count * sizeof(T), hipMemcpyHostToDevice, s), "resample upload");
-}
+constexpr const char* RS_UPLOAD = "resample upload";
 
 }  // namespace
 
@@ -212,30 +199,16 @@ int shyft_hip_resample(int device, int mode, size_t S, const int64_t* row, const
                        const int64_t* t_end, const int32_t* fx, int64_t ta_t0, int64_t ta_dt, size_t T, double* out) {
     try {
         if (rs_prepare("shyft_hip_resample", mode, S, row, t, v, t_end, fx, ta_t0, ta_dt, T, out)) return 0;
-        if (device >= 0) hip_check(hipSetDevice(device), "hipSetDevice");
-        int dev = 0;
-        hip_check(hipGetDevice(&dev), "hipGetDevice");
-        hipStream_t s = nullptr;
-        hip_check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
-        std::unique_ptr<std::remove_pointer<hipStream_t>::type, void (*)(hipStream_t)> stream(
-            s, [](hipStream_t q) { (void)hipStreamDestroy(q); });
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        hip_check(hipEventCreate(&e0), "hipEventCreate");
-        std::unique_ptr<std::remove_pointer<hipEvent_t>::type, void (*)(hipEvent_t)> ev0(
-            e0, [](hipEvent_t q) { (void)hipEventDestroy(q); });
-        hip_check(hipEventCreate(&e1), "hipEventCreate");
-        std::unique_ptr<std::remove_pointer<hipEvent_t>::type, void (*)(hipEvent_t)> ev1(
-            e1, [](hipEvent_t q) { (void)hipEventDestroy(q); });
-
+        device_call c(device);
         const size_t np = size_t(row[S]);
         dbuf<int64_t> d_row, d_t, d_tend;
         dbuf<double> d_v, d_out;
         dbuf<int32_t> d_fx;
-        rs_upload(d_row, row, S + 1, s);
-        rs_upload(d_t, t, np, s);
-        rs_upload(d_v, v, np, s);
-        rs_upload(d_tend, t_end, S, s);
-        rs_upload(d_fx, fx, S, s);
+        c.upload(d_row, row, S + 1, RS_UPLOAD);
+        c.upload(d_t, t, np, RS_UPLOAD);
+        c.upload(d_v, v, np, RS_UPLOAD);
+        c.upload(d_tend, t_end, S, RS_UPLOAD);
+        c.upload(d_fx, fx, S, RS_UPLOAD);
         d_out.alloc(T * S);
         rs_args a{};
         a.mode = mode;
@@ -253,33 +226,28 @@ int shyft_hip_resample(int device, int mode, size_t S, const int64_t* row, const
         const bool tiled = knob == SHYFT_HIP_RESAMPLE_PATH_TILED ||
                            (knob == SHYFT_HIP_RESAMPLE_PATH_AUTO && T >= size_t(RS_TILE_T));
         const size_t max_grid = size_t(1) << 20;  // the grid-stride loops take the rest
-        hip_check(hipEventRecord(e0, s), "hipEventRecord");
+        c.begin();
         if (tiled) {
             const size_t tiles = ((S + RS_TILE_S - 1) / RS_TILE_S) * ((T + RS_TILE_T - 1) / RS_TILE_T);
             hipLaunchKernelGGL(resample_tiled_kernel, dim3(unsigned(tiles < max_grid ? tiles : max_grid)), dim3(RS_BLOCK),
-                               0, s, a);
+                               0, c.s, a);
         } else {
             const size_t blocks = (T * S + RS_BLOCK - 1) / RS_BLOCK;
             hipLaunchKernelGGL(resample_direct_kernel, dim3(unsigned(blocks < max_grid ? blocks : max_grid)),
-                               dim3(RS_BLOCK), 0, s, a);
+                               dim3(RS_BLOCK), 0, c.s, a);
         }
         hip_check(hipGetLastError(), "resample");
         if (mode == SHYFT_HIP_RESAMPLE_ACCUMULATE) {
             const size_t blocks = (S + RS_BLOCK - 1) / RS_BLOCK;
             hipLaunchKernelGGL(resample_scan_kernel, dim3(unsigned(blocks < max_grid ? blocks : max_grid)), dim3(RS_BLOCK),
-                               0, s, S, T, d_out.p);
+                               0, c.s, S, T, d_out.p);
             hip_check(hipGetLastError(), "resample scan");
         }
-        hip_check(hipEventRecord(e1, s), "hipEventRecord");
-        hip_check(hipMemcpyAsync(out, d_out.p, T * S * sizeof(double), hipMemcpyDeviceToHost, s), "resample download");
-        hip_check(hipStreamSynchronize(s), "resample");
-        float ms = 0.f;
-        hip_check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-        if (dev >= 0 && dev < RS_MAX_DEVICES) {
-            g_rs_last_ms[dev].store(double(ms));
-            g_rs_last_path[dev].store(tiled ? SHYFT_HIP_RESAMPLE_PATH_TILED : SHYFT_HIP_RESAMPLE_PATH_DIRECT);
-            g_rs_calls[dev].fetch_add(1);
-        }
+        c.end();
+        c.download(out, d_out.p, T * S, "resample download");
+        g_rs_last_ms.store(c.dev, c.finish("resample"));
+        g_rs_last_path.store(c.dev, tiled ? SHYFT_HIP_RESAMPLE_PATH_TILED : SHYFT_HIP_RESAMPLE_PATH_DIRECT);
+        g_rs_calls.fetch_add(c.dev, 1);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -296,8 +264,7 @@ int shyft_hip_resample_host(int device, int mode, size_t S, const int64_t* row, 
         const double nan = std::numeric_limits<double>::quiet_NaN();
         const h::fixed_dt ta(ta_t0, ta_dt, T);
         for (size_t s = 0; s < S; ++s) {
-            const h::point_ts source(std::vector<h::utctime>(t + row[s], t + row[s + 1]), t_end[s],
-                                     std::vector<double>(v + row[s], v + row[s + 1]), h::ts_point_fx(fx[s]));
+            const h::point_ts source = point_series(s, row, t, v, t_end, fx);
             const bool linear = source.fx == h::POINT_INSTANT_VALUE;
             if (mode == SHYFT_HIP_RESAMPLE_AVERAGE) {
                 const std::vector<double> r = h::average_values(source, ta);
@@ -337,20 +304,11 @@ int shyft_hip_resample_host(int device, int mode, size_t S, const int64_t* row, 
     }
 }
 
-double shyft_hip_resample_last_ms(int device) {
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return 0.0;
-    return device >= 0 && device < RS_MAX_DEVICES ? g_rs_last_ms[device].load() : 0.0;
-}
+double shyft_hip_resample_last_ms(int device) { return g_rs_last_ms.load(device, 0.0); }
 
-uint64_t shyft_hip_resample_calls(int device) {
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return 0;
-    return device >= 0 && device < RS_MAX_DEVICES ? g_rs_calls[device].load() : 0;
-}
+uint64_t shyft_hip_resample_calls(int device) { return g_rs_calls.load(device, 0); }
 
-int shyft_hip_resample_last_path(int device) {
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return SHYFT_HIP_RESAMPLE_PATH_AUTO;
-    return device >= 0 && device < RS_MAX_DEVICES ? g_rs_last_path[device].load() : SHYFT_HIP_RESAMPLE_PATH_AUTO;
-}
+int shyft_hip_resample_last_path(int device) { return g_rs_last_path.load(device, SHYFT_HIP_RESAMPLE_PATH_AUTO); }
 
 int shyft_hip_resample_set_path(int path) {
     if (path != SHYFT_HIP_RESAMPLE_PATH_AUTO && path != SHYFT_HIP_RESAMPLE_PATH_DIRECT &&

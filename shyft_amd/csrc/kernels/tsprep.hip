@@ -53,7 +53,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <cmath>
 #include <limits>
 #include <stdexcept>
@@ -63,7 +62,8 @@
 #include "../../../detmath/detmath.h"
 #include "../device/ts_area.h"
 #include "../host/ts_prep.hpp"
-#include "../include_internal/region_impl.h"
+#include "../include_internal/device_call.h"
+#include "../include_internal/series_args.h"
 
 using namespace shyft_hip_impl;
 
@@ -397,37 +397,13 @@ __global__ __launch_bounds__(TP_BLOCK) void tp_fill_finish_kernel(tp_fill_args a
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-// The argument checks of the series, shared by the device and the host entries (those of shyft_hip_resample, with the
-// texts of host/time_series.hpp point_ts; core/time_axis.h:271-293); true when there is nothing to do.
+// The argument checks of the series, shared by the device and the host entries (include_internal/series_args.h); true
+// when there is nothing to do.
 bool tp_prepare(const char* who, size_t S, const int64_t* row, const int64_t* t, const double* v, const int64_t* t_end,
                 const int32_t* fx) {
     if (S == 0) return true;
-    if (!row || !t_end || !fx) throw std::runtime_error(std::string(who) + ": null argument");
-    if (row[0] != 0) throw std::runtime_error("tsprep: row[0] must be 0");
-    for (size_t s = 0; s < S; ++s)
-        if (row[s + 1] < row[s]) throw std::runtime_error("tsprep: row must not decrease");
-    if (row[S] > 0 && (!t || !v)) throw std::runtime_error(std::string(who) + ": null argument");
-    const int64_t i64max = std::numeric_limits<int64_t>::max(), i64min = std::numeric_limits<int64_t>::min();
-    for (size_t s = 0; s < S; ++s) {
-        if (fx[s] != int32_t(shyft_hip::host::POINT_INSTANT_VALUE) && fx[s] != int32_t(shyft_hip::host::POINT_AVERAGE_VALUE))
-            throw std::runtime_error("tsprep: fx must be POINT_INSTANT_VALUE or POINT_AVERAGE_VALUE");
-        const int64_t b = row[s], e = row[s + 1];
-        if (b == e) continue;
-        for (int64_t k = b + 1; k < e; ++k)
-            if (!(t[k - 1] < t[k])) throw std::runtime_error("time_axis::point_dt() needs time-points in increasing order");
-        if (!(t_end[s] > t[e - 1])) throw std::runtime_error("time_axis::point_dt() illegal end-of-axis");
-        // differences and sums of two times stay inside int64
-        if (t[b] < i64min / 4 || t_end[s] > i64max / 4)
-            throw std::runtime_error("tsprep: times beyond a quarter of the 64-bit range are not supported");
-    }
+    check_point_series(who, "tsprep", S, row, t, v, t_end, fx);
     return false;
-}
-
-shyft_hip::host::point_ts tp_series(size_t s, const int64_t* row, const int64_t* t, const double* v, const int64_t* t_end,
-                                    const int32_t* fx) {
-    namespace h = shyft_hip::host;
-    return h::point_ts(std::vector<h::utctime>(t + row[s], t + row[s + 1]), t_end[s],
-                       std::vector<double>(v + row[s], v + row[s + 1]), h::ts_point_fx(fx[s]));
 }
 
 // rating: the packs' CSR, pack_of, and the reference's "no rating-curve segments" for a curve without segments that a
@@ -469,9 +445,7 @@ void tp_prepare_rating(size_t S, const int64_t* row, const int64_t* t, size_t P,
 void tp_prepare_ice(size_t S, const int64_t* row, const int64_t* t, const int64_t* qrow, const int64_t* qt,
                     const int64_t* window, const double* threshold, const int32_t* policy) {
     if (!qrow || !window || !threshold || !policy) throw std::runtime_error("shyft_hip_ts_ice_packing: null argument");
-    if (qrow[0] != 0) throw std::runtime_error("tsprep: row[0] must be 0");
-    for (size_t s = 0; s < S; ++s)
-        if (qrow[s + 1] < qrow[s]) throw std::runtime_error("tsprep: row must not decrease");
+    check_csr_rows("tsprep", S, qrow);
     if (qrow[S] > 0 && !qt) throw std::runtime_error("shyft_hip_ts_ice_packing: null argument");
     const int64_t i64max = std::numeric_limits<int64_t>::max(), i64min = std::numeric_limits<int64_t>::min();
     for (size_t s = 0; s < S; ++s) {
@@ -503,52 +477,17 @@ void tp_prepare_recession(size_t S, const int64_t* row, const int64_t* t, const 
             h::ensure_overlap(h::utcperiod(ice_start[s], ice_end[s]), h::utcperiod(t[row[s]], t_end[s]));
 }
 
-constexpr int TP_MAX_DEVICES = 64;
-std::atomic<double> g_tp_last_ms[TP_MAX_DEVICES];
-std::atomic<uint64_t> g_tp_calls[TP_MAX_DEVICES];
+per_device<double> g_tp_last_ms;
+per_device<uint64_t> g_tp_calls;
+constexpr const char* TP_UPLOAD = "tsprep upload";
 
-// the stream and the two events of one device call; begin() .. end() bracket the kernels
-struct tp_call {
-    int dev = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    explicit tp_call(int device) {
-        if (device >= 0) hip_check(hipSetDevice(device), "hipSetDevice");
-        hip_check(hipGetDevice(&dev), "hipGetDevice");
-        hip_check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-            release();
-            throw std::runtime_error("hipEventCreate failed");
-        }
-    }
-    tp_call(const tp_call&) = delete;
-    tp_call& operator=(const tp_call&) = delete;
-    ~tp_call() { release(); }
-    void release() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (s) (void)hipStreamDestroy(s);
-        e0 = e1 = nullptr;
-        s = nullptr;
-    }
-    template <class T>
-    void upload(dbuf<T>& d, const T* src, size_t count) {
-        d.alloc(count);
-        if (count) hip_check(hipMemcpyAsync(d.p, src, count * sizeof(T), hipMemcpyHostToDevice, s), "tsprep upload");
-    }
-    void begin() { hip_check(hipEventRecord(e0, s), "hipEventRecord"); }
-    void end(double* out, const double* d_out, size_t count) {
-        hip_check(hipEventRecord(e1, s), "hipEventRecord");
-        hip_check(hipMemcpyAsync(out, d_out, count * sizeof(double), hipMemcpyDeviceToHost, s), "tsprep download");
-        hip_check(hipStreamSynchronize(s), "tsprep");
-        float ms = 0.f;
-        hip_check(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-        if (dev >= 0 && dev < TP_MAX_DEVICES) {
-            g_tp_last_ms[dev].store(double(ms));
-            g_tp_calls[dev].fetch_add(1);
-        }
-    }
-};
+// after the last launch: the end of the timed part, the result, and the device's counters
+void tp_finish(device_call& c, double* out, const double* d_out, size_t count) {
+    c.end();
+    c.download(out, d_out, count, "tsprep download");
+    g_tp_last_ms.store(c.dev, c.finish("tsprep"));
+    g_tp_calls.fetch_add(c.dev, 1);
+}
 
 unsigned tp_grid(size_t jobs) {
     const size_t max_grid = size_t(1) << 20;  // the grid-stride loops take the rest
@@ -557,8 +496,8 @@ unsigned tp_grid(size_t jobs) {
 }
 
 // the two scan launches of one key kind; L [np] and agg [nb] are allocated here
-void tp_scan(tp_call& c, int kind, int64_t np, int64_t S, const int64_t* d_row, const double* d_src, const double* d_min,
-             const double* d_max, dbuf<int64_t>& L, dbuf<int64_t>& agg) {
+void tp_scan(device_call& c, int kind, int64_t np, int64_t S, const int64_t* d_row, const double* d_src,
+             const double* d_min, const double* d_max, dbuf<int64_t>& L, dbuf<int64_t>& agg) {
     const int64_t nb = (np + TP_SPAN - 1) / TP_SPAN;
     L.alloc(size_t(np));
     agg.alloc(size_t(nb));
@@ -592,25 +531,25 @@ int shyft_hip_ts_rating_curve(int device, size_t S, const int64_t* row, const in
         if (tp_prepare("shyft_hip_ts_rating_curve", S, row, t, v, t_end, fx) || row[S] == 0) return 0;
         if (!out) throw std::runtime_error("shyft_hip_ts_rating_curve: null argument");
         tp_prepare_rating(S, row, t, P, pack_row, curve_t, curve_row, seg, pack_of);
-        tp_call c(device);
+        device_call c(device);
         const size_t np = size_t(row[S]), C = size_t(pack_row[P]), G = size_t(curve_row[C]);
         dbuf<int64_t> d_row, d_t, d_pack_of, d_pack_row, d_curve_t, d_curve_row;
         dbuf<double> d_v, d_seg, d_out;
-        c.upload(d_row, row, S + 1);
-        c.upload(d_t, t, np);
-        c.upload(d_v, v, np);
-        c.upload(d_pack_of, pack_of, S);
-        c.upload(d_pack_row, pack_row, P + 1);
-        c.upload(d_curve_t, curve_t, C);
-        c.upload(d_curve_row, curve_row, C + 1);
-        c.upload(d_seg, seg, 4 * G);
+        c.upload(d_row, row, S + 1, TP_UPLOAD);
+        c.upload(d_t, t, np, TP_UPLOAD);
+        c.upload(d_v, v, np, TP_UPLOAD);
+        c.upload(d_pack_of, pack_of, S, TP_UPLOAD);
+        c.upload(d_pack_row, pack_row, P + 1, TP_UPLOAD);
+        c.upload(d_curve_t, curve_t, C, TP_UPLOAD);
+        c.upload(d_curve_row, curve_row, C + 1, TP_UPLOAD);
+        c.upload(d_seg, seg, 4 * G, TP_UPLOAD);
         d_out.alloc(np);
         tp_rating_args a{int64_t(np), int64_t(S), d_row.p, d_t.p, d_v.p, d_pack_of.p, d_pack_row.p, d_curve_t.p,
                          d_curve_row.p, d_seg.p, d_out.p};
         c.begin();
         hipLaunchKernelGGL(tp_rating_kernel, dim3(tp_grid(np)), dim3(TP_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsprep rating");
-        c.end(out, d_out.p, np);
+        tp_finish(c, out, d_out.p, np);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -638,7 +577,8 @@ int shyft_hip_ts_rating_curve_host(int device, size_t S, const int64_t* row, con
                 packs[p].add_curve(curve_t[c], f);
             }
         for (size_t s = 0; s < S; ++s) {
-            const std::vector<double> r = h::rating_curve_values(tp_series(s, row, t, v, t_end, fx), packs[pack_of[s]]);
+            const h::point_ts level = point_series(s, row, t, v, t_end, fx);
+            const std::vector<double> r = h::rating_curve_values(level, packs[pack_of[s]]);
             std::copy(r.begin(), r.end(), out + row[s]);
         }
         return 0;
@@ -655,28 +595,28 @@ int shyft_hip_ts_ice_packing(int device, size_t S, const int64_t* row, const int
         tp_prepare_ice(S, row, t, qrow, qt, window, threshold, policy);
         if (qrow[S] == 0) return 0;
         if (!out) throw std::runtime_error("shyft_hip_ts_ice_packing: null argument");
-        tp_call c(device);
+        device_call c(device);
         const size_t np = size_t(row[S]), nq = size_t(qrow[S]);
         dbuf<int64_t> d_row, d_t, d_tend, d_qrow, d_qt, d_window;
         dbuf<double> d_v, d_thr, d_out;
         dbuf<int32_t> d_fx, d_policy;
-        c.upload(d_row, row, S + 1);
-        c.upload(d_t, t, np);
-        c.upload(d_v, v, np);
-        c.upload(d_tend, t_end, S);
-        c.upload(d_fx, fx, S);
-        c.upload(d_qrow, qrow, S + 1);
-        c.upload(d_qt, qt, nq);
-        c.upload(d_window, window, S);
-        c.upload(d_thr, threshold, S);
-        c.upload(d_policy, policy, S);
+        c.upload(d_row, row, S + 1, TP_UPLOAD);
+        c.upload(d_t, t, np, TP_UPLOAD);
+        c.upload(d_v, v, np, TP_UPLOAD);
+        c.upload(d_tend, t_end, S, TP_UPLOAD);
+        c.upload(d_fx, fx, S, TP_UPLOAD);
+        c.upload(d_qrow, qrow, S + 1, TP_UPLOAD);
+        c.upload(d_qt, qt, nq, TP_UPLOAD);
+        c.upload(d_window, window, S, TP_UPLOAD);
+        c.upload(d_thr, threshold, S, TP_UPLOAD);
+        c.upload(d_policy, policy, S, TP_UPLOAD);
         d_out.alloc(nq);
         tp_ice_args a{int64_t(nq), int64_t(S), d_row.p, d_t.p, d_v.p, d_tend.p, d_fx.p, d_qrow.p, d_qt.p, d_window.p,
                       d_thr.p, d_policy.p, d_out.p};
         c.begin();
         hipLaunchKernelGGL(tp_ice_kernel, dim3(tp_grid(nq)), dim3(TP_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsprep ice packing");
-        c.end(out, d_out.p, nq);
+        tp_finish(c, out, d_out.p, nq);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -694,7 +634,7 @@ int shyft_hip_ts_ice_packing_host(int device, size_t S, const int64_t* row, cons
         if (qrow[S] == 0) return 0;
         if (!out) throw std::runtime_error("shyft_hip_ts_ice_packing_host: null argument");
         for (size_t s = 0; s < S; ++s) {
-            const h::point_ts temp = tp_series(s, row, t, v, t_end, fx);
+            const h::point_ts temp = point_series(s, row, t, v, t_end, fx);
             const h::ice_packing_parameters ip{window[s], threshold[s]};
             for (int64_t j = qrow[s]; j < qrow[s + 1]; ++j)
                 out[j] = h::detect_ice_packing(temp, ip, h::ice_packing_temperature_policy(policy[s]), qt[j]);
@@ -713,18 +653,18 @@ int shyft_hip_ts_ice_packing_recession(int device, size_t S, const int64_t* row,
         if (tp_prepare("shyft_hip_ts_ice_packing_recession", S, row, t, v, t_end, fx) || row[S] == 0) return 0;
         if (!out) throw std::runtime_error("shyft_hip_ts_ice_packing_recession: null argument");
         tp_prepare_recession(S, row, t, t_end, ice, ice_start, ice_end, alpha, recession_minimum);
-        tp_call c(device);
+        device_call c(device);
         const size_t np = size_t(row[S]);
         dbuf<int64_t> d_row, d_t, L, agg;
         dbuf<double> d_v, d_ice, d_alpha, d_qmin, d_out;
         dbuf<int32_t> d_fx;
-        c.upload(d_row, row, S + 1);
-        c.upload(d_t, t, np);
-        c.upload(d_v, v, np);
-        c.upload(d_fx, fx, S);
-        c.upload(d_ice, ice, np);
-        c.upload(d_alpha, alpha, S);
-        c.upload(d_qmin, recession_minimum, S);
+        c.upload(d_row, row, S + 1, TP_UPLOAD);
+        c.upload(d_t, t, np, TP_UPLOAD);
+        c.upload(d_v, v, np, TP_UPLOAD);
+        c.upload(d_fx, fx, S, TP_UPLOAD);
+        c.upload(d_ice, ice, np, TP_UPLOAD);
+        c.upload(d_alpha, alpha, S, TP_UPLOAD);
+        c.upload(d_qmin, recession_minimum, S, TP_UPLOAD);
         d_out.alloc(np);
         c.begin();
         tp_scan(c, TP_KEY_RECESSION, int64_t(np), int64_t(S), d_row.p, d_ice.p, nullptr, nullptr, L, agg);
@@ -732,7 +672,7 @@ int shyft_hip_ts_ice_packing_recession(int device, size_t S, const int64_t* row,
                       d_out.p};
         hipLaunchKernelGGL(tp_rec_finish_kernel, dim3(tp_grid(np)), dim3(TP_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsprep recession");
-        c.end(out, d_out.p, np);
+        tp_finish(c, out, d_out.p, np);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -750,7 +690,7 @@ int shyft_hip_ts_ice_packing_recession_host(int device, size_t S, const int64_t*
         if (!out) throw std::runtime_error("shyft_hip_ts_ice_packing_recession_host: null argument");
         tp_prepare_recession(S, row, t, t_end, ice, ice_start, ice_end, alpha, recession_minimum);
         for (size_t s = 0; s < S; ++s) {
-            const h::point_ts flow = tp_series(s, row, t, v, t_end, fx);
+            const h::point_ts flow = point_series(s, row, t, v, t_end, fx);
             const std::vector<double> ice_at(ice + row[s], ice + row[s + 1]);
             const h::ice_packing_recession_parameters ipr{alpha[s], recession_minimum[s]};
             for (size_t i = 0; i < flow.size(); ++i) out[row[s] + int64_t(i)] = h::ice_packing_recession_value(flow, ice_at, ipr, i);
@@ -767,16 +707,16 @@ int shyft_hip_ts_min_max_fill(int device, size_t S, const int64_t* row, const in
     try {
         if (tp_prepare("shyft_hip_ts_min_max_fill", S, row, t, v, t_end, fx) || row[S] == 0) return 0;
         if (!out || !min_x || !max_x || !max_timespan) throw std::runtime_error("shyft_hip_ts_min_max_fill: null argument");
-        tp_call c(device);
+        device_call c(device);
         const size_t np = size_t(row[S]);
         dbuf<int64_t> d_row, d_t, d_span, Lp, aggp, Lq, aggq;
         dbuf<double> d_v, d_min, d_max, d_out;
-        c.upload(d_row, row, S + 1);
-        c.upload(d_t, t, np);
-        c.upload(d_v, v, np);
-        c.upload(d_min, min_x, S);
-        c.upload(d_max, max_x, S);
-        c.upload(d_span, max_timespan, S);
+        c.upload(d_row, row, S + 1, TP_UPLOAD);
+        c.upload(d_t, t, np, TP_UPLOAD);
+        c.upload(d_v, v, np, TP_UPLOAD);
+        c.upload(d_min, min_x, S, TP_UPLOAD);
+        c.upload(d_max, max_x, S, TP_UPLOAD);
+        c.upload(d_span, max_timespan, S, TP_UPLOAD);
         d_out.alloc(np);
         c.begin();
         tp_scan(c, TP_KEY_FILL, int64_t(np), int64_t(S), d_row.p, d_v.p, d_min.p, d_max.p, Lp, aggp);
@@ -785,7 +725,7 @@ int shyft_hip_ts_min_max_fill(int device, size_t S, const int64_t* row, const in
                        aggq.p, d_out.p};
         hipLaunchKernelGGL(tp_fill_finish_kernel, dim3(tp_grid(np)), dim3(TP_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsprep fill");
-        c.end(out, d_out.p, np);
+        tp_finish(c, out, d_out.p, np);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -802,7 +742,7 @@ int shyft_hip_ts_min_max_fill_host(int device, size_t S, const int64_t* row, con
         if (!out || !min_x || !max_x || !max_timespan)
             throw std::runtime_error("shyft_hip_ts_min_max_fill_host: null argument");
         for (size_t s = 0; s < S; ++s) {
-            const h::point_ts ts = tp_series(s, row, t, v, t_end, fx);
+            const h::point_ts ts = point_series(s, row, t, v, t_end, fx);
             h::qac_parameter p;
             p.max_timespan = max_timespan[s];
             p.min_x = min_x[s];
@@ -815,14 +755,8 @@ int shyft_hip_ts_min_max_fill_host(int device, size_t S, const int64_t* row, con
     }
 }
 
-double shyft_hip_tsprep_last_ms(int device) {
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return 0.0;
-    return device >= 0 && device < TP_MAX_DEVICES ? g_tp_last_ms[device].load() : 0.0;
-}
+double shyft_hip_tsprep_last_ms(int device) { return g_tp_last_ms.load(device, 0.0); }
 
-uint64_t shyft_hip_tsprep_calls(int device) {
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return 0;
-    return device >= 0 && device < TP_MAX_DEVICES ? g_tp_calls[device].load() : 0;
-}
+uint64_t shyft_hip_tsprep_calls(int device) { return g_tp_calls.load(device, 0); }
 
 }  // extern "C"

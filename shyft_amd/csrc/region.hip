@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/shyft_hip.h"
+#include "include_internal/device_call.h"
 #include "include_internal/kernels.h"
 #include "include_internal/layout.h"
 #include "include_internal/region_impl.h"
@@ -1036,15 +1037,10 @@ int shyft_hip_btk(int device, size_t n_sources, const double* src_xyz, const dou
                 for (size_t d = 0; d < n_dst; ++d) out[t * n_dst + d] = src_values[t];
             return 0;
         }
-        if (device >= 0) hip_check(hipSetDevice(device), "hipSetDevice");
-        hipStream_t s = nullptr;
-        hip_check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
-        std::unique_ptr<std::remove_pointer<hipStream_t>::type, void (*)(hipStream_t)> stream(
-            s, [](hipStream_t x) { (void)hipStreamDestroy(x); });
+        device_call c(device);
         dbuf<double> d_xyz, d_out;
-        d_xyz.alloc(3 * n_dst);
+        c.upload(d_xyz, dst_xyz, 3 * n_dst, "upload");
         d_out.alloc(n * n_dst);
-        hip_check(hipMemcpyAsync(d_xyz.p, dst_xyz, 3 * n_dst * sizeof(double), hipMemcpyHostToDevice, s), "upload");
         btk_args a{};
         a.n_sources = n_sources;
         a.src_xyz = src_xyz;
@@ -1061,9 +1057,9 @@ int shyft_hip_btk(int device, size_t n_sources, const double* src_xyz, const dou
         a.d_dst_index = nullptr;
         a.d_out = d_out.p;
         a.ld_out = n_dst;
-        btk_run(a, s);
-        hip_check(hipMemcpyAsync(out, d_out.p, n * n_dst * sizeof(double), hipMemcpyDeviceToHost, s), "download");
-        hip_check(hipStreamSynchronize(s), "sync");
+        btk_run(a, c.s);
+        c.download(out, d_out.p, n * n_dst, "download");
+        c.sync("sync");
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -1109,23 +1105,18 @@ int shyft_hip_ordinary_kriging(int device, size_t n_sources, const double* src_x
     try {
         ok_args a{};
         if (ok_prepare(n_sources, src_values, n, ok_param, n_dst, out, a)) return 0;
-        if (device >= 0) hip_check(hipSetDevice(device), "hipSetDevice");
-        hipStream_t s = nullptr;
-        hip_check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
-        std::unique_ptr<std::remove_pointer<hipStream_t>::type, void (*)(hipStream_t)> stream(
-            s, [](hipStream_t x) { (void)hipStreamDestroy(x); });
+        device_call c(device);
         dbuf<double> d_xyz, d_out;
-        d_xyz.alloc(3 * n_dst);
+        c.upload(d_xyz, dst_xyz, 3 * n_dst, "upload");
         d_out.alloc(n * n_dst);
-        hip_check(hipMemcpyAsync(d_xyz.p, dst_xyz, 3 * n_dst * sizeof(double), hipMemcpyHostToDevice, s), "upload");
         a.src_xyz = src_xyz;
         a.dst_xyz = dst_xyz;
         a.d_dst_xyz = d_xyz.p;
         a.d_out = d_out.p;
         a.ld_out = n_dst;
-        ok_run(a, s);
-        hip_check(hipMemcpyAsync(out, d_out.p, n * n_dst * sizeof(double), hipMemcpyDeviceToHost, s), "download");
-        hip_check(hipStreamSynchronize(s), "sync");
+        ok_run(a, c.s);
+        c.download(out, d_out.p, n * n_dst, "download");
+        c.sync("sync");
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());

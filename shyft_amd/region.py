@@ -564,11 +564,8 @@ def resample(series, time_axis, mode: int = RESAMPLE_AVERAGE, device: int = -1, 
     return resample_csr(row, t, v, t_end, fx, t0, dt, T, mode, device=device, host=host)
 
 
-def resample_csr(row, t, v, t_end, fx, ta_t0: int, ta_dt: int, T: int, mode: int = RESAMPLE_AVERAGE, device: int = -1,
-                 host: bool = False) -> np.ndarray:
-    """resample on the arrays of the C ABI: row [S+1] point offsets, t [row[S]] int64 microseconds, v [row[S]],
-    t_end [S] int64 microseconds, fx [S] (0 POINT_INSTANT_VALUE, 1 POINT_AVERAGE_VALUE), and the axis in
-    microseconds. Returns [T][S]."""
+def _csr_series(what, row, t, v, t_end, fx):
+    """S point series in the CSR form of the C ABI as contiguous arrays of its types, shapes checked"""
     row = np.ascontiguousarray(row, dtype=np.int64).reshape(-1)
     t = np.ascontiguousarray(t, dtype=np.int64).reshape(-1)
     v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
@@ -576,9 +573,18 @@ def resample_csr(row, t, v, t_end, fx, ta_t0: int, ta_dt: int, T: int, mode: int
     fx = np.ascontiguousarray(fx, dtype=np.int32).reshape(-1)
     S = row.shape[0] - 1
     if S < 0 or t_end.shape[0] != S or fx.shape[0] != S:
-        raise ValueError("resample: row must have one entry more than t_end and fx")
+        raise ValueError(f"{what}: row must have one entry more than t_end and fx")
     if t.shape[0] != v.shape[0] or (S and (row[0] != 0 or row[-1] != t.shape[0])):
-        raise ValueError("resample: row must run from 0 to the number of points")
+        raise ValueError(f"{what}: row must run from 0 to the number of points")
+    return S, row, t, v, t_end, fx
+
+
+def resample_csr(row, t, v, t_end, fx, ta_t0: int, ta_dt: int, T: int, mode: int = RESAMPLE_AVERAGE, device: int = -1,
+                 host: bool = False) -> np.ndarray:
+    """resample on the arrays of the C ABI: row [S+1] point offsets, t [row[S]] int64 microseconds, v [row[S]],
+    t_end [S] int64 microseconds, fx [S] (0 POINT_INSTANT_VALUE, 1 POINT_AVERAGE_VALUE), and the axis in
+    microseconds. Returns [T][S]."""
+    S, row, t, v, t_end, fx = _csr_series("resample", row, t, v, t_end, fx)
     out = np.empty((int(T), S), dtype=np.float64)
     fn = lib().shyft_hip_resample_host if host else lib().shyft_hip_resample
     check(fn(device, int(mode), S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), int(ta_t0), int(ta_dt), int(T),
@@ -611,20 +617,6 @@ def resample_last_path(device: int = -1) -> int:
 ICE_DISALLOW_MISSING, ICE_ALLOW_INITIAL_MISSING, ICE_ALLOW_ANY_MISSING = 0, 1, 2
 
 
-def _tsprep_series(what, row, t, v, t_end, fx):
-    row = np.ascontiguousarray(row, dtype=np.int64).reshape(-1)
-    t = np.ascontiguousarray(t, dtype=np.int64).reshape(-1)
-    v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
-    t_end = np.ascontiguousarray(t_end, dtype=np.int64).reshape(-1)
-    fx = np.ascontiguousarray(fx, dtype=np.int32).reshape(-1)
-    S = row.shape[0] - 1
-    if S < 0 or t_end.shape[0] != S or fx.shape[0] != S:
-        raise ValueError(f"{what}: row must have one entry more than t_end and fx")
-    if t.shape[0] != v.shape[0] or (S and (row[0] != 0 or row[-1] != t.shape[0])):
-        raise ValueError(f"{what}: row must run from 0 to the number of points")
-    return S, row, t, v, t_end, fx
-
-
 def _per_series(what, name, x, S, dtype):
     """one value for all series, or one per series"""
     a = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
@@ -642,7 +634,7 @@ def ts_rating_curve_csr(row, t, v, t_end, fx, pack_row, curve_t, curve_row, seg,
     the CSR form of resample_csr. The packs are a three-level CSR: pack_row [P+1] -> curve_t [C] curve start times
     (int64 microseconds) -> curve_row [C+1] -> seg [G][4] = lower, a, b, c; pack_of names the pack of each series (one
     value for all, or [S]). host=True runs the host restatement, which the device is bit-identical to."""
-    S, row, t, v, t_end, fx = _tsprep_series("ts_rating_curve", row, t, v, t_end, fx)
+    S, row, t, v, t_end, fx = _csr_series("ts_rating_curve", row, t, v, t_end, fx)
     pack_row = np.ascontiguousarray(pack_row, dtype=np.int64).reshape(-1)
     curve_t = np.ascontiguousarray(curve_t, dtype=np.int64).reshape(-1)
     curve_row = np.ascontiguousarray(curve_row, dtype=np.int64).reshape(-1)
@@ -666,7 +658,7 @@ def ts_ice_packing_csr(row, t, v, t_end, fx, qrow, qt, window, threshold, policy
     core/time_series.h:1808-1831): 1.0 when the average over [t - window, t) is below the threshold, 0.0 when not, NaN
     when the policy cannot tell. window (int64 microseconds), threshold and policy (ICE_*) are one value for all
     series or [S]. Pass qrow=row, qt=t for the series' own points."""
-    S, row, t, v, t_end, fx = _tsprep_series("ts_ice_packing", row, t, v, t_end, fx)
+    S, row, t, v, t_end, fx = _csr_series("ts_ice_packing", row, t, v, t_end, fx)
     qrow = np.ascontiguousarray(qrow, dtype=np.int64).reshape(-1)
     qt = np.ascontiguousarray(qt, dtype=np.int64).reshape(-1)
     if qrow.shape[0] != S + 1 or (S and (qrow[0] != 0 or qrow[-1] != qt.shape[0])):
@@ -687,7 +679,7 @@ def ts_ice_packing_recession_csr(row, t, v, t_end, fx, ice, ice_start, ice_end, 
     at the flow's points) says ice-packing, one value per point (shyft_hip_ts_ice_packing_recession;
     ice_packing_recession_ts::evaluate, core/time_series_dd.h:1323-1354). ice_start / ice_end [S] are the indicator's
     total period (the flow's must lie inside); alpha [1/s] and recession_minimum are one value for all or [S]."""
-    S, row, t, v, t_end, fx = _tsprep_series("ts_ice_packing_recession", row, t, v, t_end, fx)
+    S, row, t, v, t_end, fx = _csr_series("ts_ice_packing_recession", row, t, v, t_end, fx)
     ice = np.ascontiguousarray(ice, dtype=np.float64).reshape(-1)
     if ice.shape[0] != t.shape[0]:
         raise ValueError("ts_ice_packing_recession: ice must hold one value per flow point")
@@ -708,7 +700,7 @@ def ts_min_max_fill_csr(row, t, v, t_end, fx, min_x, max_x, max_timespan, device
     line through its nearest valid neighbours, or NaN when they are missing or more than max_timespan (int64
     microseconds) apart, one value per point (shyft_hip_ts_min_max_fill; qac_ts::value,
     core/time_series_dd.cpp:1335-1376). The three parameters are one value for all series or [S]."""
-    S, row, t, v, t_end, fx = _tsprep_series("ts_min_max_fill", row, t, v, t_end, fx)
+    S, row, t, v, t_end, fx = _csr_series("ts_min_max_fill", row, t, v, t_end, fx)
     min_x = _per_series("ts_min_max_fill", "min_x", min_x, S, np.float64)
     max_x = _per_series("ts_min_max_fill", "max_x", max_x, S, np.float64)
     span = _per_series("ts_min_max_fill", "max_timespan", max_timespan, S, np.int64)
