@@ -514,6 +514,50 @@ int shyft_hip_ts_min_max_fill_host(int device, size_t S, const int64_t* row, con
 double shyft_hip_tsprep_last_ms(int device);
 uint64_t shyft_hip_tsprep_calls(int device);
 
+/* Forecast skill by lead time: the Nash-Sutcliffe score of P problems in one launch of kernels/forecast.hip on a device
+ * (device < 0 = current). A problem is ats_vector::nash_sutcliffe(obs, t0_offset, dt, n)
+ * (core/time_series_dd.cpp:1137-1145 -> core/time_series_merge.h:123-144): for each forecast in order the n slice
+ * averages of the forecast and of the observation on the axis (forecast.time(0) + t0_offset, dt, n)
+ * (average_accessor with USE_NAN, core/time_series.h:2033-2072), appended forecast-major, then
+ * 1 - nash_sutcliffe_goal_function(observed, forecast) (core/time_series.h:2316-2344), whose two sums run sequentially
+ * in that order over the pairs where both values are finite. The slice averages alone are
+ * ats_vector::average_slice (time_series_dd.cpp:1147-1165). It replaces one average_accessor pass per forecast per
+ * lead time on one thread. Host pointers, stateless.
+ *
+ * The S series are one pool in the CSR form of shyft_hip_resample (row [S+1], t and v [row[S]], t_end [S], fx [S]);
+ * forecasts and observations sit together, so a lead-time table lists the same forecasts under many problems and
+ * uploads their points once. Problem p names its forecasts fc_ix[fc_row[p] .. fc_row[p+1]) by index into the pool, in
+ * the reference's order, and its observation obs_ix[p] (-1: none), and carries t0_offset[p], dt[p] (ticks) and n[p].
+ * J is the sum over p of F_p * n[p]; job (p, k, i) lies at job_row[p] + k * n[p] + i with job_row the running sum.
+ * sim and obs ([J], or NULL) receive the slice averages of forecast k and of the observation over
+ * [t[row[f]] + t0_offset[p] + i * dt[p], + dt[p]): NaN when the period starts at or after the series' end, else
+ * area / to_seconds(tsum), NaN without covered time; obs is NaN throughout for obs_ix == -1 or an observation without
+ * points. ns ([P], or NULL) receives the score: NaN when F_p * n[p] == 0 and, by the division, without finite pairs;
+ * a constant observation gives -inf or NaN. No special cases are added.
+ *
+ * Checked on the host before anything is launched, by both twins with the same texts: the series as for
+ * shyft_hip_resample; fc_row a CSR row; every index in [0, S), or -1 for obs_ix; a forecast has at least one point
+ * ("forecast_skill: a forecast has no points": the reference asks an empty axis for time(0)); n >= 0, dt > 0,
+ * t0_offset >= 0 with the texts of time_series_dd.cpp:1138-1143; every slice axis inside a quarter of the int64 range;
+ * a one-point observation whose point lies strictly inside a period of any forecast's axis of its problems is an
+ * error, as in the reference (point_dt::time throws). A refused batch launches nothing; P == 0 or J == 0 returns 0
+ * and launches nothing, after writing NaN to ns. Every operation is evaluated as written (int64 ticks, to_seconds as
+ * a division, no FMA) and the sums keep the reference's order (no tree reduction), so ns, sim and obs are
+ * bit-identical to shyft_hip_forecast_skill_host, which runs host/forecast.hpp on one thread and does not use
+ * `device`. */
+int shyft_hip_forecast_skill(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                             const int64_t* t_end, const int32_t* fx, size_t P, const int64_t* fc_row,
+                             const int64_t* fc_ix, const int64_t* obs_ix, const int64_t* t0_offset, const int64_t* dt,
+                             const int64_t* n, double* ns, double* sim, double* obs);
+int shyft_hip_forecast_skill_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                                  const int64_t* t_end, const int32_t* fx, size_t P, const int64_t* fc_row,
+                                  const int64_t* fc_ix, const int64_t* obs_ix, const int64_t* t0_offset,
+                                  const int64_t* dt, const int64_t* n, double* ns, double* sim, double* obs);
+/* HIP-event milliseconds of the kernel of the last shyft_hip_forecast_skill on this device, copies excluded, and the
+ * number of such calls that launched so far. (No reference counterpart: measurement and test aid.) */
+double shyft_hip_forecast_skill_last_ms(int device);
+uint64_t shyft_hip_forecast_skill_calls(int device);
+
 size_t shyft_hip_number_of_catchments(const shyft_hip_region* h);
 int shyft_hip_catchment_ids(const shyft_hip_region* h, int64_t* cids);
 

@@ -89,6 +89,11 @@ SIGNATURES = {
     "shyft_hip_ts_min_max_fill_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 9),
     "shyft_hip_tsprep_last_ms": (C.c_double, [C.c_int]),
     "shyft_hip_tsprep_calls": (C.c_uint64, [C.c_int]),
+    "shyft_hip_forecast_skill": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 9),
+    "shyft_hip_forecast_skill_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t]
+                                      + [C.c_void_p] * 9),
+    "shyft_hip_forecast_skill_last_ms": (C.c_double, [C.c_int]),
+    "shyft_hip_forecast_skill_calls": (C.c_uint64, [C.c_int]),
     "shyft_hip_synthetic_elevation": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]),
     "shyft_hip_run_cells": (C.c_int, [_h, C.c_size_t, C.c_int, C.c_int]),
     "shyft_hip_run_cells_async": (C.c_int, [_h, C.c_int, C.c_int]),

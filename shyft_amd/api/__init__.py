@@ -364,6 +364,117 @@ class TsVector(_Vector):
     def min_max_check_linear_fill(self, v_min, v_max, dt_max=_tsprep.max_utctime, *, host=False):
         return _tsprep.min_max_check_linear_fill(self, v_min, v_max, dt_max, host)
 
+    # forecast skill by lead time and the forecast merge (time_series_dd.cpp:1120-1165, api_time_series.cpp:299-339)
+    def average_slice(self, lead_time, delta_t, n, *, host=False):
+        """the true average of every series over n slices of delta_t that start lead_time after the series' own first
+        point, all in one device call (region.forecast_skill_csr), or with host=True on the host, bit-identical.
+        Series k of the result is POINT_AVERAGE_VALUE on TimeAxis(ts_k.time(0) + lead_time, delta_t, n); a series
+        without points is passed through unchanged."""
+        from ..region import forecast_skill_csr
+        _check_slice_arguments(lead_time, delta_t, n)
+        filled = [k for k, ts in enumerate(self) if ts.size()]
+        out = TsVector(self)
+        if not filled:
+            return out
+        csr = _api._series_csr([self[k]._ts for k in filled])
+        P = len(filled)
+        _, sim, _ = forecast_skill_csr(*csr, np.arange(P + 1), np.arange(P), np.full(P, -1), _api._to_us(lead_time),
+                                       _api._to_us(delta_t), int(n), host=host, slices=True)
+        for j, k in enumerate(filled):
+            ta = TimeAxisFixedDeltaT(self[k].time(0) + lead_time, delta_t, int(n))
+            out[k] = TimeSeries(_impl=_api._PointTs(ta, sim[j * int(n):(j + 1) * int(n)], POINT_AVERAGE_VALUE))
+        return out
+
+    def nash_sutcliffe(self, observation_ts, lead_time, delta_t, n, *, host=False):
+        """the Nash-Sutcliffe score (1 is a perfect match) of these forecasts against observation_ts over n slices of
+        delta_t that start lead_time into each forecast, in one device call, or with host=True on the host,
+        bit-identical. NaN for an empty vector or an empty observation."""
+        _check_slice_arguments(lead_time, delta_t, n)
+        if len(self) == 0 or observation_ts.size() == 0:  # time_series_merge.h:126-127
+            return float("nan")
+        if int(n) == 0:  # nash_sutcliffe_goal_function, core/time_series.h:2318-2319
+            raise RuntimeError("nash_sutcliffe needs equal sized ts accessors with elements >1")
+        return float(forecast_skill(TsVectorSet([self]), TsVector([observation_ts]), [lead_time], delta_t, n,
+                                    host=host)[0, 0])
+
+    def forecast_merge(self, lead_time, fc_interval):
+        """one series from the slice [time(0) + lead_time, + fc_interval) of every forecast, a missing forecast filled
+        from its neighbours (forecast_merge, core/time_series_merge.h:47-99), on the host. The forecasts are ordered by
+        start time, at least fc_interval apart, and each reaches the end of its slice."""
+        if lead_time < 0:  # time_series_dd.cpp:1120-1133
+            raise RuntimeError("lead_time parameter should be 0 or a positive number giving number of seconds into each "
+                               "forecast to start the merge slice")
+        if fc_interval <= 0:
+            raise RuntimeError("fc_interval parameter should be positive number giving number of seconds between first "
+                               "time point in each of the supplied forecast")
+        for i in range(1, len(self)):
+            if self[i - 1].total_period().start + fc_interval > self[i].total_period().start:
+                raise RuntimeError("The suplied forecast vector should be strictly ordered by increasing t0 by length at "
+                                   f"least fc_interval: requirement broken at index:{i}")
+        return TimeSeries(_impl=_api._forecast_merge([ts._ts for ts in self], lead_time, fc_interval))
+
+
+def _check_slice_arguments(lead_time, delta_t, n):
+    """the argument texts of ats_vector::nash_sutcliffe and average_slice (time_series_dd.cpp:1138-1143, 1148-1153)"""
+    if n < 0:
+        raise RuntimeError("n, number of intervals, must be specified as > 0")
+    if delta_t <= 0:
+        raise RuntimeError("dt, average interval, must be specified as > 0 s")
+    if lead_time < 0:
+        raise RuntimeError("lead_time,t0_offset,must be specified  >= 0 s")
+
+
+def forecast_skill(forecast_sets, observations, lead_times, delta_t, n, *, host=False):
+    """The Nash-Sutcliffe score by location and lead time, the whole table in one device call
+    (region.forecast_skill_csr; an MI355X addition without a reference counterpart). forecast_sets is a TsVectorSet
+    with one TsVector of forecasts per location, observations a TsVector with one observation per location. Returns an
+    ndarray [len(forecast_sets)][len(lead_times)] whose cell [l][j] equals
+    forecast_sets[l].nash_sutcliffe(observations[l], lead_times[j], delta_t, n), bit for bit. host=True runs the host
+    restatement."""
+    from ..region import forecast_skill_csr
+    L, lead_times = len(forecast_sets), list(lead_times)
+    if len(observations) != L:
+        raise RuntimeError(f"forecast_skill: {L} forecast sets need {L} observations, got {len(observations)}")
+    for lead in lead_times or [0]:
+        _check_slice_arguments(lead, delta_t, n)
+    scored = [len(forecast_sets[l]) > 0 and observations[l].size() > 0 for l in range(L)]
+    if int(n) == 0 and lead_times and any(scored):
+        raise RuntimeError("nash_sutcliffe needs equal sized ts accessors with elements >1")
+    pool, fc_of, obs_of = [], [], []  # the series of all locations once; a location's rows of the table share them
+    for l in range(L):
+        first = len(pool)
+        if scored[l]:
+            pool.extend(ts._ts for ts in forecast_sets[l])
+        fc_of.append(range(first, len(pool)))
+        obs_of.append(len(pool) if scored[l] else -1)
+        if scored[l]:
+            pool.append(observations[l]._ts)
+    fc_row, fc_ix, obs_ix, offsets = [0], [], [], []
+    for l in range(L):
+        for lead in lead_times:
+            fc_ix.extend(fc_of[l])
+            fc_row.append(len(fc_ix))
+            obs_ix.append(obs_of[l])
+            offsets.append(_api._to_us(lead))
+    ns = forecast_skill_csr(*_api._series_csr(pool), fc_row, fc_ix, obs_ix, offsets, _api._to_us(delta_t), int(n),
+                            host=host)
+    return ns.reshape(L, len(lead_times))
+
+
+def nash_sutcliffe(observation_ts, model_ts, time_axis):
+    """api.nash_sutcliffe (time_series_dd.cpp:950-954): 1 - the Nash-Sutcliffe goal function over the true averages
+    of the two series on time_axis, on the host; 1.0 is a perfect match."""
+    return 1.0 - _api.nash_sutcliffe_goal_function(list(observation_ts.average(time_axis)._ts._values),
+                                                   list(model_ts.average(time_axis)._ts._values))
+
+
+def kling_gupta(observation_ts, model_ts, time_axis, s_r, s_a, s_b):
+    """api.kling_gupta (time_series_dd.cpp:956-960): 1 - the Kling-Gupta goal function with the scale factors s_r
+    (correlation), s_a (variability) and s_b (bias) over the true averages of the two series on time_axis, on the
+    host; 1.0 is a perfect match."""
+    return 1.0 - _api.kling_gupta_goal_function(list(observation_ts.average(time_axis)._ts._values),
+                                                list(model_ts.average(time_axis)._ts._values), s_r, s_a, s_b)
+
 
 class TsFactory:
     """api.TsFactory (api/api.h:1630-1700)."""

@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "calibration.hpp"
+#include "forecast.hpp"
 #include "kalman.hpp"
 #include "qm.hpp"
 #include "region_model.hpp"
@@ -28,6 +29,31 @@ namespace {
 
 utctime to_us(double seconds) { return utctime(std::llround(seconds * 1e6)); }
 double to_s(utctime us) { return double(us) / 1e6; }
+
+// the point series of a list as the CSR arrays of the batched series entries: (row, t, v, t_end, fx)
+py::tuple series_csr(const py::list& series) {
+    std::vector<const point_ts*> src;
+    for (auto h : series) src.push_back(&h.cast<const point_ts&>());
+    const size_t S = src.size();
+    const py::ssize_t n_series = py::ssize_t(S);
+    py::array_t<int64_t> row(n_series + 1), t_end(n_series);
+    py::array_t<int32_t> fx(n_series);
+    int64_t* r = row.mutable_data();
+    r[0] = 0;
+    for (size_t s = 0; s < S; ++s) {
+        r[s + 1] = r[s] + int64_t(src[s]->size());
+        t_end.mutable_data()[s] = src[s]->t_end;
+        fx.mutable_data()[s] = int32_t(src[s]->fx);
+    }
+    const py::ssize_t n_points = py::ssize_t(r[S]);
+    py::array_t<int64_t> t(n_points);
+    py::array_t<double> v(n_points);
+    for (size_t s = 0; s < S; ++s) {
+        std::copy(src[s]->t.begin(), src[s]->t.end(), t.mutable_data() + r[s]);
+        std::copy(src[s]->v.begin(), src[s]->v.end(), v.mutable_data() + r[s]);
+    }
+    return py::make_tuple(row, t, v, t_end, fx);
+}
 
 template <class Stack>
 void bind_model(py::module_& m, const char* name) {
@@ -603,27 +629,16 @@ PYBIND11_MODULE(_api, m) {
     // The host work of region.resample: the point series of a list as the CSR arrays of shyft_hip_resample (row, t, v,
     // t_end, fx) and the axis in microseconds (t0, dt, n).
     m.def("_resample_plan", [](const py::list& series, const fixed_dt& ta) {
-        std::vector<const point_ts*> src;
-        for (auto h : series) src.push_back(&h.cast<const point_ts&>());
-        const size_t S = src.size();
-        const py::ssize_t n_series = py::ssize_t(S);
-        py::array_t<int64_t> row(n_series + 1), t_end(n_series);
-        py::array_t<int32_t> fx(n_series);
-        int64_t* r = row.mutable_data();
-        r[0] = 0;
-        for (size_t s = 0; s < S; ++s) {
-            r[s + 1] = r[s] + int64_t(src[s]->size());
-            t_end.mutable_data()[s] = src[s]->t_end;
-            fx.mutable_data()[s] = int32_t(src[s]->fx);
-        }
-        const py::ssize_t n_points = py::ssize_t(r[S]);
-        py::array_t<int64_t> t(n_points);
-        py::array_t<double> v(n_points);
-        for (size_t s = 0; s < S; ++s) {
-            std::copy(src[s]->t.begin(), src[s]->t.end(), t.mutable_data() + r[s]);
-            std::copy(src[s]->v.begin(), src[s]->v.end(), v.mutable_data() + r[s]);
-        }
-        return py::make_tuple(row, t, v, t_end, fx, int64_t(ta.t), int64_t(ta.dt), ta.size());
+        return series_csr(series) + py::make_tuple(int64_t(ta.t), int64_t(ta.dt), ta.size());
+    });
+    // The host work of region.forecast_skill_csr callers: the CSR arrays alone, and seconds as ticks.
+    m.def("_series_csr", &series_csr);
+    m.def("_to_us", &to_us);
+    // TsVector.forecast_merge (host/forecast.hpp; core/time_series_merge.h:47-99)
+    m.def("_forecast_merge", [](const py::list& series, double lead_time, double fc_interval) {
+        std::vector<const point_ts*> tsv;
+        for (auto h : series) tsv.push_back(&h.cast<const point_ts&>());
+        return forecast_merge(tsv, to_us(lead_time), to_us(fc_interval));
     });
     py::class_<interpolation_parameter>(m, "InterpolationParameter")
         .def(py::init<>())

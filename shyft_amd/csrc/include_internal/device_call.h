@@ -1,5 +1,5 @@
 // Internal, host-only: what the stateless batched entries (shyft_hip_kalman_run, _quantile_map, _resample, the
-// shyft_hip_ts_* entries, shyft_hip_btk, shyft_hip_ordinary_kriging) share on the host side of one device call.
+// shyft_hip_ts_* entries, _forecast_skill, shyft_hip_btk, shyft_hip_ordinary_kriging) share on the host side of one device call.
 #pragma once
 #include <atomic>
 

@@ -719,3 +719,46 @@ def tsprep_last_ms(device: int = -1) -> float:
 def tsprep_calls(device: int = -1) -> int:
     """The number of ts_*_csr device calls that launched on the device so far."""
     return int(lib().shyft_hip_tsprep_calls(device))
+
+
+# ---- forecast skill by lead time (kernels/forecast.hip) ---------------------------------------------------------------
+def forecast_skill_csr(row, t, v, t_end, fx, fc_row, fc_ix, obs_ix, t0_offset, dt, n, device: int = -1,
+                       host: bool = False, slices: bool = False):
+    """The Nash-Sutcliffe score of P problems in one device call (shyft_hip_forecast_skill; nash_sutcliffe of
+    core/time_series_merge.h:123-144). The S series, forecasts and observations together, are in the CSR form of
+    resample_csr. Problem p takes the forecasts fc_ix[fc_row[p]:fc_row[p+1]] (indexes into the series) against the
+    observation obs_ix[p] (-1: none) over n[p] slices of dt[p] that start t0_offset[p] after each forecast's first
+    point (int64 microseconds; one value for all problems, or [P]). Returns ns [P]; with slices=True (ns, sim, obs),
+    the slice averages of every forecast and of the observation, [sum of F_p * n[p]] in problem, forecast, slice
+    order. host=True runs the host restatement, which the device is bit-identical to."""
+    S, row, t, v, t_end, fx = _csr_series("forecast_skill", row, t, v, t_end, fx)
+    fc_row = np.ascontiguousarray(fc_row, dtype=np.int64).reshape(-1)
+    fc_ix = np.ascontiguousarray(fc_ix, dtype=np.int64).reshape(-1)
+    obs_ix = np.ascontiguousarray(obs_ix, dtype=np.int64).reshape(-1)
+    P = fc_row.shape[0] - 1
+    if P < 0 or obs_ix.shape[0] != P:
+        raise ValueError("forecast_skill: fc_row must have one entry more than obs_ix")
+    if P and (fc_row[0] != 0 or fc_row[-1] != fc_ix.shape[0]):
+        raise ValueError("forecast_skill: fc_row must run from 0 to the number of forecast indexes")
+    t0_offset = _per_series("forecast_skill", "t0_offset", t0_offset, P, np.int64)
+    dt = _per_series("forecast_skill", "dt", dt, P, np.int64)
+    n = _per_series("forecast_skill", "n", n, P, np.int64)
+    ns = np.empty(P, dtype=np.float64)
+    sim = obs = None
+    if slices:
+        J = int(np.sum(np.diff(fc_row) * np.maximum(n, 0), dtype=np.int64)) if P else 0
+        sim, obs = np.full(J, np.nan), np.full(J, np.nan)
+    fn = lib().shyft_hip_forecast_skill_host if host else lib().shyft_hip_forecast_skill
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), P, _ptr(fc_row), _ptr(fc_ix), _ptr(obs_ix),
+             _ptr(t0_offset), _ptr(dt), _ptr(n), _ptr(ns), _ptr(sim), _ptr(obs)), None)
+    return (ns, sim, obs) if slices else ns
+
+
+def forecast_skill_last_ms(device: int = -1) -> float:
+    """HIP-event milliseconds of the kernel of the last forecast_skill_csr device call on the device, copies excluded."""
+    return float(lib().shyft_hip_forecast_skill_last_ms(device))
+
+
+def forecast_skill_calls(device: int = -1) -> int:
+    """The number of forecast_skill_csr device calls that launched on the device so far."""
+    return int(lib().shyft_hip_forecast_skill_calls(device))
