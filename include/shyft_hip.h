@@ -658,6 +658,8 @@ int shyft_hip_math_selftest(int fn, const double* x, const double* y, size_t n, 
  *   BRENT          (pt_gs_k)          z1, a1, b1, a2, b2, mode    gs_corr_lwc, gs_corr_lwc_lean
  *   BRENT_SPEC4 / BRENT_SPEC2         the same                    gs_corr_lwc_spec on 4 / 2 lanes per job, then
  *                                                                 gs_corr_lwc_memo, as the small-region run kernel
+ *   BRENT_OPEN4 / BRENT_OPEN2         the same                    gs_brent_job_open in groups of 4 / 2 lanes per
+ *                                                                 job, as the 256-lane run kernels call it
  *   SKAUGEN        (pt_ss_k)          u, n, nu_a, alpha           ss_sca_rel_red, its error code
  *   SKAUGEN_GROUP2 / SKAUGEN_GROUP4   the same                    ss_sca_rel_red_group on 2 / 4 lanes per job
  * Brent mode 0: Q1 is not supplied (q1 = NaN, the job evaluates it); mode 1: q1 = calc_q(a1, b1, z1). */
@@ -672,6 +674,8 @@ int shyft_hip_math_selftest(int fn, const double* x, const double* y, size_t n, 
 #define SHYFT_HIP_DST_SKAUGEN 8
 #define SHYFT_HIP_DST_SKAUGEN_GROUP2 9
 #define SHYFT_HIP_DST_SKAUGEN_GROUP4 10
+#define SHYFT_HIP_DST_BRENT_OPEN4 11
+#define SHYFT_HIP_DST_BRENT_OPEN2 12
 int shyft_hip_device_selftest(int fn, const double* in, size_t n_in_cols, size_t n, double* out, size_t n_out_cols);
 
 #ifdef __cplusplus

@@ -48,6 +48,14 @@ struct gsb_f {
         ap1 = a2 + 1.0;
         a_ok = a2 > 0.0;
     }
+    // with Q1 already formed
+    __device__ __forceinline__ gsb_f(double a2_, double b2_, double lga2_, double Q1_)
+        : a2(a2_), b2(b2_), lga2(lga2_), Q1(Q1_) {
+        k = gsb_load();
+        eps = detmath::gamma_snow_policy_eps(a2);
+        ap1 = a2 + 1.0;
+        a_ok = a2 > 0.0;
+    }
     __device__ __forceinline__ double operator()(double z) const {
         bool ok;
         double cq = gsb_calc_q(a2, b2, z, lga2, eps, ap1, k, ok);
@@ -186,5 +194,167 @@ __device__ __noinline__ double gs_corr_lwc_memo(double z1, double a1, double b1,
                                                 double lga2, const gsb_memo& memo) {
     return gs_corr_lwc_lean_t<true>(z1, a1, b1, a2, b2, q1, lga2, &memo);
 }
+
+// ---- the job entry of the 256-lane instances: the opening on the solving wavefront's idle lanes.
+//
+// The workgroup's job queue is one LDS array [GSQ_ROWS][B] (kernels/ptgsk.hip). A group of L = 4 or 2 neighbouring
+// lanes of the solving wavefront (lanes L j .. L j + L - 1, in hardware lane order) enters with job j; L = 1 is one
+// lane per job without an opening. Lane k of the group evaluates f at gs_brent_point(z1, k) -- one pass of the
+// wavefront for the points that brent_find_minima would visit in two (L = 2) or three (L = 4) -- the group's first
+// lane takes the siblings' (z, f) by cross-lane reads, the siblings return, and the first lane runs the solver from
+// its first iteration: in iteration 1 (and 2 when L = 4) fu is the sibling's f when u's bits equal the sibling's
+// point; otherwise the lane leaves the peeled iterations as it entered that iteration and the loop evaluates f(u)
+// as ever. f is a pure function of its argument, so a hit is the same bits and a wrong guess is only a miss. The
+// loop that follows the peeled iterations is gs_corr_lwc_lean's with its live state (no memo). The result goes to
+// row GSQ_RES of job j. Every lane of a group must enter together (the cross-lane reads return 0 from a lane that
+// is not executing).
+enum { GSQ_Z1, GSQ_A1, GSQ_B1, GSQ_A2, GSQ_B2, GSQ_Q1, GSQ_LG2, GSQ_RES, GSQ_ROWS };
+typedef __attribute__((address_space(3))) double gsq_lds;
+
+// brent_find_minima's iteration on the solver's local variables, in two halves (statement macros: the state stays
+// in registers): up to its point u (go = false: the tolerance test ended the search), and from fu = f(u) on
+#define GSB_NEXT_POINT(go)                                                                                          \
+    do {                                                                                                            \
+        mid = (min + max) / 2;                                                                                      \
+        fract1 = tolerance * fabs(x) + tolerance / 4;                                                               \
+        fract2 = 2 * fract1;                                                                                        \
+        go = !(fabs(x - mid) <= (fract2 - (max - min) / 2));                                                        \
+        if (!go) break;                                                                                             \
+        if (fabs(delta2) > fract1) {                                                                                \
+            double r = (x - w) * (fx - fv);                                                                         \
+            double q = (x - v) * (fx - fw);                                                                         \
+            double p = (x - v) * q - (x - w) * r;                                                                   \
+            q = 2 * (q - r);                                                                                        \
+            if (q > 0) p = -p;                                                                                      \
+            q = fabs(q);                                                                                            \
+            double td = delta2;                                                                                     \
+            delta2 = delta;                                                                                         \
+            if ((fabs(p) >= fabs(q * td / 2)) || (p <= q * (min - x)) || (p >= q * (max - x))) {                    \
+                delta2 = (x >= mid) ? min - x : max - x;                                                            \
+                delta = golden * delta2;                                                                            \
+            } else {                                                                                                \
+                delta = p / q;                                                                                      \
+                u = x + delta;                                                                                      \
+                if (((u - min) < fract2) || ((max - u) < fract2))                                                   \
+                    delta = (mid - x) < 0 ? -fabs(fract1) : fabs(fract1);                                           \
+            }                                                                                                       \
+        } else {                                                                                                    \
+            delta2 = (x >= mid) ? min - x : max - x;                                                                \
+            delta = golden * delta2;                                                                                \
+        }                                                                                                           \
+        u = (fabs(delta) >= fract1) ? (x + delta) : (delta > 0 ? x + fabs(fract1) : x - fabs(fract1));              \
+    } while (0)
+#define GSB_TAKE()                                                                                                  \
+    do {                                                                                                            \
+        if (fu <= fx) {                                                                                             \
+            if (u >= x) min = x; else max = x;                                                                      \
+            v = w; w = x; x = u;                                                                                    \
+            fv = fw; fw = fx; fx = fu;                                                                              \
+        } else {                                                                                                    \
+            if (u < x) min = u; else max = u;                                                                       \
+            if ((fu <= fw) || (w == x)) {                                                                           \
+                v = w; w = u; fv = fw; fw = fu;                                                                     \
+            } else if ((fu <= fv) || (v == x) || (v == w)) {                                                        \
+                v = u; fv = fu;                                                                                     \
+            }                                                                                                       \
+        }                                                                                                           \
+    } while (0)
+
+// lanes per job in a workgroup-step with nj jobs. MODE 2: four with at most 16 jobs, two with at most 32, else one;
+// MODE 1: four or one; MODE 0: one
+template <int MODE>
+__device__ __forceinline__ int gs_brent_group(int nj) {
+    return (MODE >= 1 && nj <= 16) ? 4 : (MODE >= 2 && nj <= 32) ? 2 : 1;
+}
+
+// t: the lane in the solver's lane order (kernels/ptgsk.hip), L: the step's lanes per job (uniform). The caller
+// enters with the lanes t < L nj.
+template <int B>
+__device__ __noinline__ void gs_brent_job_open(gsq_lds* jq_, int t, int L_) {
+    // (the queue's base and L are uniform: scalar registers)
+    const int L = __builtin_amdgcn_readfirstlane(L_);
+    gsq_lds* const jq = (gsq_lds*)(uintptr_t)__builtin_amdgcn_readfirstlane((int)(uintptr_t)jq_);
+    const int j = L == 4 ? t >> 2 : L == 2 ? t >> 1 : t;
+    const double z1 = jq[GSQ_Z1 * B + j];
+#ifdef SHYFT_ABLATE_BRENT
+    if (((int)__lane_id() & (L - 1)) == 0) jq[GSQ_RES * B + j] = z1 * 0.5;  // instruction-budget ablation only (wrong results)
+    return;
+#endif
+    const gsb_f fe(z1, jq[GSQ_A1 * B + j], jq[GSQ_B1 * B + j], jq[GSQ_A2 * B + j], jq[GSQ_B2 * B + j],
+                   jq[GSQ_Q1 * B + j], jq[GSQ_LG2 * B + j]);
+    double min = 0.0, max = z1;
+    const double tolerance = 0x1p-11;  // ldexp(1, 1-12)
+    const double golden = (double)0.3819660f;
+    double x, w, v, u, delta, delta2, fu, fv, fw, fx, mid, fract1, fract2;
+    x = w = v = max;
+    delta2 = delta = 0;
+    // the job index above the iteration count: one register in the loop
+    static_assert(B <= (1 << 16), "job index field");
+    int count = (j << 8) | 60;
+    bool go = true;
+    {
+        // the opening: lane k at point k, then the siblings' points and values to the group's first lane
+        const int lane = (int)__lane_id(), k = lane & (L - 1), g0 = lane & ~(L - 1);  // (L = 1: point 0)
+        u = gs_brent_point(z1, k);
+        fu = fe(u);
+        double sz1 = 0.0, sf1 = 0.0, sz2 = 0.0, sf2 = 0.0, sz3 = 0.0, sf3 = 0.0;
+        if (L >= 2) {
+            sz1 = __shfl(u, g0 + 1);
+            sf1 = __shfl(fu, g0 + 1);
+        }
+        if (L == 4) {
+            sz2 = __shfl(u, g0 + 2);
+            sf2 = __shfl(fu, g0 + 2);
+            sz3 = __shfl(u, g0 + 3);
+            sf3 = __shfl(fu, g0 + 3);
+        }
+        if (k != 0) return;
+        fw = fv = fx = fu;  // x = w = v = z1 = u
+        // the peeled iterations. A miss puts delta and delta2 back and leaves: the loop below then forms the same u
+        // from the same state and evaluates it
+        if (L >= 2) do {
+            GSB_NEXT_POINT(go);  // iteration 1: u1
+            if (!go) break;
+            if (__double_as_longlong(u) != __double_as_longlong(sz1)) {
+                delta2 = delta = 0;
+                break;
+            }
+            fu = sf1;
+            GSB_TAKE();
+            --count;
+            if (L == 4) {
+                const double d = delta, d2 = delta2;
+                GSB_NEXT_POINT(go);  // iteration 2: u2a or u2b
+                if (!go) break;
+                if (__double_as_longlong(u) == __double_as_longlong(sz2)) fu = sf2;
+                else if (__double_as_longlong(u) == __double_as_longlong(sz3)) fu = sf3;
+                else {
+                    delta = d;
+                    delta2 = d2;
+                    break;
+                }
+                GSB_TAKE();
+                --count;
+            }
+        } while (0);
+    }
+    if (go) do {  // gs_corr_lwc_lean's loop
+        GSB_NEXT_POINT(go);
+        if (!go) break;
+        // a2 + 1 and the policy eps are formed again in each trip (the same values) instead of being held across
+        // the loop: the two registers that otherwise make the allocator spill one of f's constants to scratch and
+        // reload it in every trip
+        double a2o = fe.a2;
+        asm volatile("" : "+v"(a2o));
+        gsb_f fl = fe;
+        fl.ap1 = a2o + 1.0;
+        fl.eps = detmath::gamma_snow_policy_eps(a2o);
+        fu = fl(u);
+        GSB_TAKE();
+    } while (--count & 0xff);
+    jq[GSQ_RES * B + (count >> 8)] = x;
+}
+#undef GSB_NEXT_POINT
+#undef GSB_TAKE
 
 }  // namespace shyft_dev

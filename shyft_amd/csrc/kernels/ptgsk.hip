@@ -93,6 +93,14 @@ constexpr int BRENT_PRIO = 3;
 #define SHYFT_PTGSK_LGQ_JOBLG 1
 #endif
 
+// the Brent opening on the solving wavefront's idle lanes in the 256-lane instances (gs_brent_job_open,
+// device/gs_brent.h): 0, one lane per job whatever the job count (gs_corr_lwc_lean, for A/B builds); 1, four lanes
+// per job in a workgroup-step with at most 16 jobs; 2, that and two lanes per job with 17-32 jobs. A step with more
+// jobs has one lane per job as before, through the same entry
+#ifndef SHYFT_PTGSK_BOPEN
+#define SHYFT_PTGSK_BOPEN 2
+#endif
+
 // UNIFORM: every cell of the launch uses parameter set 0 (the region parameter, no catchment overrides):
 // the parameter row is then wave-uniform and lives in SGPRs (scalar loads), which frees the VGPRs the
 // per-lane copies would take in the register-bound time loop.
@@ -186,6 +194,7 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
     lcc[10][threadIdx.x] = 0.0;
     constexpr bool LGQ = SHYFT_PTGSK_LGQ != 0 && B == 256 && !SPEC;
     constexpr bool JOBLG = LGQ && SHYFT_PTGSK_LGQ_JOBLG != 0;
+    constexpr int BOPEN = (B == 256 && !SPEC) ? SHYFT_PTGSK_BOPEN : 0;
     lgamma_cache_lds<JOBLG> lgc{lcc[9], lcc[10]};
     gs_carry carry;
     int32_t err = 0;
@@ -207,7 +216,21 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
     // Brent job queue of the workgroup (COMPACT)
     // (jres is not aliased with a job array: a lane reads its result after the step's second barrier, and another
     // wavefront may already be enqueueing the next step's jobs by then)
-    __shared__ double jz1[B], ja1[B], jb1[B], ja2[B], jb2[B], jq1[B], jlg2[B], jres[B];
+    // (the 256-lane instances: one array, rows GSQ_* of device/gs_brent.h, whose base gs_brent_job_open takes. The
+    // 64-lane instance keeps its eight arrays: with one array its code needs 168 VGPRs instead of 175, which lets a
+    // third wavefront onto a SIMD, and a small region's two workgroups per SIMD then spread unevenly: 25 % slower at
+    // 131,072 cells)
+    __shared__ double jq[SPEC ? 1 : GSQ_ROWS][SPEC ? 1 : B];
+    __shared__ double sz1[SPEC ? B : 1], sa1[SPEC ? B : 1], sb1[SPEC ? B : 1], sa2[SPEC ? B : 1], sb2[SPEC ? B : 1],
+        sq1[SPEC ? B : 1], slg2[SPEC ? B : 1], sres[SPEC ? B : 1];
+    double* const jz1 = SPEC ? sz1 : jq[GSQ_Z1];
+    double* const ja1 = SPEC ? sa1 : jq[GSQ_A1];
+    double* const jb1 = SPEC ? sb1 : jq[GSQ_B1];
+    double* const ja2 = SPEC ? sa2 : jq[GSQ_A2];
+    double* const jb2 = SPEC ? sb2 : jq[GSQ_B2];
+    double* const jq1 = SPEC ? sq1 : jq[GSQ_Q1];
+    double* const jlg2 = SPEC ? slg2 : jq[GSQ_LG2];
+    double* const jres = SPEC ? sres : jq[GSQ_RES];
     __shared__ double jsz[SPEC ? 64 : 1], jsf[SPEC ? 64 : 1];  // speculative opening: point and f of lane t
     __shared__ int jcount[2];
     // lgamma queue of the workgroup (LGQ): the lanes whose final calc_snow_state of the step will want lgamma of a
@@ -288,15 +311,27 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
         };
         // JOBLG: the jobs' lgamma(a2) ahead of the solves, by the lane that solves the job; it also goes to the
         // owner's slot unless the owner has queued another shape since (the keys are final after the first barrier)
-        auto brent_jobs = [&](int first, int nj) {
+        // t: the lane in the solver's lane order (0-63: the solving wavefront, whose hardware lanes they are).
+        // With at most 16 (32) jobs the solving wavefront has 4 (2) lanes per job: lane t enters job t / L with its
+        // group, which opens the search on its L lanes at once (gs_brent_job_open); the lgamma(a2) of job j has
+        // been written by lane j of the same wavefront just before (LDS operations of a wavefront execute in order;
+        // the fence keeps the compiler from moving them).
+        auto brent_jobs = [&](int t, int nj) {
             if (JOBLG)
-                for (int j = first; j < nj; j += B) {
+                for (int j = t; j < nj; j += B) {
                     const double lga2 = dlgamma(ja2[j]);
                     jlg2[j] = lga2;
                     const int o = jown[j];
                     if (lcc[9][o] == ja2[j]) lcc[10][o] = lga2;
                 }
-            for (int j = first; j < nj; j += B)
+            if (BOPEN) {
+                // (a group's lanes are all below 64: L nj <= 64)
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                const int L = gs_brent_group<BOPEN>(nj);
+                for (int tt = t; tt < L * nj; tt += B) gs_brent_job_open<B>((gsq_lds*)&jq[0][0], tt, L);
+                return;
+            }
+            for (int j = t; j < nj; j += B)
                 jres[j] = GS_BRENT_JOB(jz1[j], ja1[j], jb1[j], ja2[j], jb2[j], jq1[j], jlg2[j]);
         };
         // dlgamma of the queued shapes first, first + stride, ... into their owners' value slots
@@ -483,6 +518,7 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
 #ifndef SHYFT_PTGSK_BUDGET_WAVES
 #define SHYFT_PTGSK_BUDGET_WAVES 7
 #endif
+constexpr int ST_BOPEN = SHYFT_PTGSK_BOPEN ? SHYFT_PTGSK_BOPEN : 2;  // the job entry that the selftest kernel runs
 __global__ __launch_bounds__(256, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_callee_budget_kernel(const ptgsk_kargs a) {
     if (a.n_cells >= 0) return;  // never runs: launch_ptgsk_run only references it
     const int c = threadIdx.x;
@@ -497,7 +533,11 @@ __global__ __launch_bounds__(256, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_callee_bu
              [&](double z1, double a1, double b1, double a2, double b2, double q1, double lga2) {
                  j[0] = z1; j[1] = a1; j[2] = b1; j[3] = a2; j[4] = b2; j[5] = q1; j[6] = lga2;
              });
-    const double z = gs_corr_lwc_lean(j[0], j[1], j[2], j[3], j[4], j[5], j[6]);
+    double z = gs_corr_lwc_lean(j[0], j[1], j[2], j[3], j[4], j[5], j[6]);
+    __shared__ double jq[GSQ_ROWS][BLOCK];
+    for (int r = 0; r < 7; ++r) jq[r][c] = j[r];
+    gs_brent_job_open<BLOCK>((gsq_lds*)&jq[0][0], c, 4);
+    z += jq[GSQ_RES][c];
     gs_back(s, m, z, sca, sto, outf, c == 1, a.dt_us, a.params, gc, q, lgc, carry);
     double e;
     const double pe = pt_pot_evap_exp<true>(0.2, 1.26, q, q, q, q, e);
@@ -507,7 +547,7 @@ __global__ __launch_bounds__(256, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_callee_bu
 
 // ---- diagnostic kernels (shyft_hip_device_selftest): this file's device functions on chosen inputs, one thread per
 // row, in [col][n] -> out [col][n]. They live here so that the out-of-line functions they call (dexp, dlog, dexp2,
-// dlgamma, gs_gamma_pq_general, gs_corr_lwc_lean, gs_corr_lwc_spec, gs_corr_lwc_memo ...) are the instances the run
+// dlgamma, gs_gamma_pq_general, gs_corr_lwc_lean, gs_brent_job_open, gs_corr_lwc_spec ...) are the instances the run
 // kernels call, and they carry the occupancy bounds of a kernel that already calls those functions (the callee
 // budget kernel's, or the speculative instance's), so the functions are compiled as before.
 constexpr int ST_BLOCK = 256;
@@ -620,6 +660,31 @@ __global__ __launch_bounds__(64, 2) void ptgsk_st_brent_spec_kernel(const double
     }
 }
 
+// gs_brent_job_open as the 256-lane run kernels call it: a 256-lane workgroup with the [GSQ_ROWS][256] queue, JOBS
+// jobs per workgroup (16: groups of 4 lanes; 32: groups of 2), the first wavefront's lanes in groups per job. The
+// last workgroup is ragged and takes the group size of its own job count, as a workgroup-step does.
+template <int JOBS>
+__global__ __launch_bounds__(ST_BLOCK, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_st_brent_open_kernel(
+    const double* __restrict__ in, size_t n, double* __restrict__ out) {
+    static_assert(JOBS == 16 || JOBS == 32, "16 or 32 jobs per workgroup");
+    __shared__ double jq[GSQ_ROWS][ST_BLOCK];
+    const int t = threadIdx.x;
+    const size_t j0 = blockIdx.x * (size_t)JOBS;
+    const int nj = n - j0 < (size_t)JOBS ? (int)(n - j0) : JOBS;  // the launch has no workgroup beyond the jobs
+    if (t < nj) {
+        const size_t i = j0 + t;
+        jq[GSQ_Z1][t] = in[i]; jq[GSQ_A1][t] = in[n + i]; jq[GSQ_B1][t] = in[2 * n + i];
+        jq[GSQ_A2][t] = in[3 * n + i]; jq[GSQ_B2][t] = in[4 * n + i];
+        jq[GSQ_Q1][t] = st_brent_q1(in[5 * n + i], jq[GSQ_Z1][t], jq[GSQ_A1][t], jq[GSQ_B1][t]);
+        jq[GSQ_LG2][t] = dlgamma(jq[GSQ_A2][t]);
+    }
+    __syncthreads();
+    const int L = gs_brent_group<ST_BOPEN>(nj);
+    if (t < L * nj) gs_brent_job_open<ST_BLOCK>((gsq_lds*)&jq[0][0], t, L);
+    __syncthreads();
+    if (t < nj) out[j0 + t] = jq[GSQ_RES][t];
+}
+
 }  // namespace
 
 
@@ -656,8 +721,9 @@ hipError_t launch_ptgsk_run(const ptgsk_kargs& a, hipStream_t stream) {
         if (a.uniform_params) hipLaunchKernelGGL((ptgsk_run_kernel<true, true, false, SHYFT_LB_WAVES, BLOCK, false, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
         else hipLaunchKernelGGL((ptgsk_run_kernel<true, false, false, SHYFT_LB_WAVES, BLOCK, false, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
     } else {
-        // (the speculative Brent opening in this instance measured 100.5 -> 134.7 ms per 1M-cell chunk, year mean:
-        // its memo registers spill in every phase of the 128-VGPR step loop, so it stays a small-region feature)
+        // (the small-region instance's speculative opening -- a memo the step loop loads and hands to the solver, a
+        // workgroup barrier between the points and the solve -- measured slower in the 256-lane instances, twice;
+        // they open the search inside the job entry instead: gs_brent_job_open)
         if (a.uniform_params) hipLaunchKernelGGL((ptgsk_run_kernel<true, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
         else hipLaunchKernelGGL((ptgsk_run_kernel<true, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
     }
@@ -678,6 +744,12 @@ hipError_t launch_ptgsk_selftest(int fn, const double* in, size_t n, double* out
             break;
         case SHYFT_HIP_DST_BRENT_SPEC2:  // 32 jobs
             hipLaunchKernelGGL(ptgsk_st_brent_spec_kernel<2>, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, stream, in, n, out);
+            break;
+        case SHYFT_HIP_DST_BRENT_OPEN4:  // 16 jobs per workgroup, on its first wavefront
+            hipLaunchKernelGGL(ptgsk_st_brent_open_kernel<16>, dim3((unsigned)((n + 15) / 16)), block, 0, stream, in, n, out);
+            break;
+        case SHYFT_HIP_DST_BRENT_OPEN2:  // 32 jobs
+            hipLaunchKernelGGL(ptgsk_st_brent_open_kernel<32>, dim3((unsigned)((n + 31) / 32)), block, 0, stream, in, n, out);
             break;
         default: return hipErrorInvalidValue;
     }

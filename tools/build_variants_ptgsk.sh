@@ -2,6 +2,8 @@
 # Fast variant build: recompile only kernels/ptgsk.hip with extra flags and link it with the
 # regular objects in shyft_amd/csrc/_obj (run `make -C shyft_amd/csrc` first).
 # usage: build_variants_ptgsk.sh name1 "flags1" name2 "flags2" ...
+# e.g. the Brent opening A/B:
+#   build_variants_ptgsk.sh bopen0 "-DSHYFT_PTGSK_BOPEN=0" bopen1 "-DSHYFT_PTGSK_BOPEN=1" bopen2 "-DSHYFT_PTGSK_BOPEN=2"
 # PTGSK_FLAGS: the Makefile's per-object flags of this file (set it empty to build a variant without them)
 set -e
 cd "$(dirname "$0")/../shyft_amd/csrc"
