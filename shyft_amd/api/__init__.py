@@ -865,6 +865,34 @@ class _FlatParameter:
         return c
 
 
+class _SnowDistributionParameter(_FlatParameter):
+    """A stack parameter with the hbv_snow / hbv_physical_snow quantile distribution (hbv_snow.h:21-72,
+    hbv_physical_snow.h:43-74): snow_s (bin weights) and snow_intervals ride behind the flat vector as
+    n_bins, s[MAX_BINS], intervals[MAX_BINS]."""
+    SNOW_MODEL = "hbv_snow"  # named in the bin-count error
+    MAX_BINS = 8
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        src = a[0] if a and isinstance(a[0], _SnowDistributionParameter) else None
+        self.snow_s = list(src.snow_s) if src else [1.0] * 5
+        self.snow_intervals = list(src.snow_intervals) if src else [0.0, 0.25, 0.5, 0.75, 1.0]
+
+    def to_vector(self):
+        nb, mb = len(self.snow_s), self.MAX_BINS
+        if not 2 <= nb <= mb or len(self.snow_intervals) != nb:
+            raise RuntimeError(f"{self.SNOW_MODEL}: number of snow bins must be in [2, {mb}]")
+        # normalize_snow_distribution (hbv_snow.h:63-66): s /= integrate(s, intervals) over the whole range,
+        # the trapezoid sum of hbv_snow_common.h:14-40 with a = intervals[0], b = intervals[-1]
+        x, f = self.snow_intervals, self.snow_s
+        area = 0.0
+        for k in range(nb - 1):
+            area += 0.5 * (f[k] + f[k + 1]) * (x[k + 1] - x[k])
+        s = [v / area for v in f] + [0.0] * (mb - nb)
+        i = list(self.snow_intervals) + [0.0] * (mb - nb)
+        return list(self._v) + [float(nb)] + s + i
+
+
 class _FlatState:
     NAMES: tuple = ()
     DEFAULTS: tuple = ()
@@ -1304,3 +1332,48 @@ from ._api import (  # noqa: E402,F401
     nash_sutcliffe_goal_function, kling_gupta_goal_function, rmse_goal_function, abs_diff_sum_goal_function,
     abs_diff_sum_goal_function_scaled,
 )
+
+
+# ---- the model types of a method stack (expose.h:143-170, :447-458) --------------------------------------------------
+def _make_models(prefix, base_cls, native_model, native_optimizer, docs):
+    """(Model, OptModel, create_opt_model_clone, create_full_model_clone, Optimizer) of a stack: the region models
+    with the all-response and the discharge collector (`<prefix>Model`, `<prefix>OptModel`, docstrings `docs`) over
+    the stack's _ModelMixin subclass base_cls and its C++ host class native_model, and their optimizer type."""
+    from ._calibration import make_optimizer_type
+    parameter_t = base_cls._parameter_t
+
+    def construct(self, full, args, devices, shard_flags):
+        if len(args) == 1 and isinstance(args[0], native_model):  # a deep copy of another model of the stack
+            other = args[0]
+            native_model.__init__(self, other, full)
+            self._region_parameter = parameter_t(other._region_parameter)
+            self._catchment_parameters = {k: parameter_t(v) for k, v in other._catchment_parameters.items()}
+            self._ip, self._env = other._ip, other._env  # the reference shares region_env (region_model.h:446-448)
+            return
+        geo, region_param = args[0], args[1]
+        cps = args[2] if len(args) > 2 else {}
+        native_model.__init__(self, list(geo), region_param.to_vector(),
+                              {int(k): v.to_vector() for k, v in cps.items()}, full,
+                              [int(d) for d in (devices or [])], int(shard_flags))
+        self._init_python(region_param, cps)
+
+    def model_type(name, full, doc):
+        def __init__(self, *args, devices=None, shard_flags=0):
+            construct(self, full, args, devices, shard_flags)
+        return type(name, (base_cls, native_model),
+                    {"__init__": __init__, "__doc__": doc, "__module__": base_cls.__module__})
+
+    model = model_type(prefix + "Model", True, docs[0])
+    opt_model = model_type(prefix + "OptModel", False, docs[1])
+
+    def create_opt_model_clone(src_model):
+        return opt_model(src_model)
+
+    def create_full_model_clone(src_model):
+        return model(src_model)
+
+    # the model types know their optimizer, parameter and state types (expose.h:147-170, model_calibrator)
+    optimizer = make_optimizer_type(prefix + "Optimizer", native_optimizer)
+    for m in (model, opt_model):
+        m.optimizer_t, m.parameter_t, m.state_t = optimizer, parameter_t, base_cls._state_t
+    return model, opt_model, create_opt_model_clone, create_full_model_clone, optimizer

@@ -2,8 +2,8 @@
 shyft/api/pt_gs_k/__init__.py:5-63) over the MI355X engine."""
 from __future__ import annotations
 
-from .. import (_api, _FlatParameter, _FlatState, _ModelMixin, _Statistics, _Vector, SERIES_STATE,
-                make_state_with_id_types)
+from .. import (_api, _FlatParameter, _FlatState, _make_models, _ModelMixin, _Statistics, _Vector,
+                SERIES_STATE, make_state_with_id_types)
 
 # get/set order and names of pt_gs_k::parameter (core/pt_gs_k.h:77-112, get_name :155-190), defaults of the
 # member structs (kirchner.h:120-125, gamma_snow.h:46-97, priestley_taylor.h, routing.h:76, mstack_param.h)
@@ -87,58 +87,23 @@ class _PTGSKBase(_ModelMixin):
         return _Statistics(self, {"output": (6, True), "pot_ratio": ("pot_ratio", True)})
 
 
-def _ctor(self, base, full, args, devices=None, shard_flags=0):
-    if len(args) == 1 and isinstance(args[0], (_api._PTGSKRegionModel,)):
-        other = args[0]
-        base.__init__(self, other, full)
-        self._region_parameter = PTGSKParameter(other._region_parameter)
-        self._catchment_parameters = {k: PTGSKParameter(v) for k, v in other._catchment_parameters.items()}
-        self._ip, self._env = other._ip, other._env  # the reference shares region_env (region_model.h:446-448)
-        return
-    geo, region_param = args[0], args[1]
-    cps = args[2] if len(args) > 2 else {}
-    base.__init__(self, list(geo), region_param.to_vector(), {int(k): v.to_vector() for k, v in cps.items()}, full,
-                  [int(d) for d in (devices or [])], int(shard_flags))
-    self._init_python(region_param, cps)
+PTGSKModel, PTGSKOptModel, _opt_clone, _full_clone, PTGSKOptimizer = _make_models(
+    "PTGSK", _PTGSKBase, _api._PTGSKRegionModel, _api._PTGSKOptimizer,
+    ("region_model<pt_gs_k cell_complete_response_t> (pt_gs_k.cpp:146, all_response_collector).",
+     "region_model<pt_gs_k cell_discharge_response_t> (pt_gs_k.cpp:147, discharge_collector)."))
 
 
-class PTGSKModel(_PTGSKBase, _api._PTGSKRegionModel):
-    """region_model<pt_gs_k cell_complete_response_t> (pt_gs_k.cpp:146, all_response_collector)."""
-
-    def __init__(self, *args, devices=None, shard_flags=0):
-        _ctor(self, _api._PTGSKRegionModel, True, args, devices, shard_flags)
-
-
-class PTGSKOptModel(_PTGSKBase, _api._PTGSKRegionModel):
-    """region_model<pt_gs_k cell_discharge_response_t> (pt_gs_k.cpp:147, discharge_collector)."""
-
-    def __init__(self, *args, devices=None, shard_flags=0):
-        _ctor(self, _api._PTGSKRegionModel, False, args, devices, shard_flags)
+def _without_catchment_params(m, keep):
+    if not keep:
+        for cid in list(m._catchment_parameters):
+            m.remove_catchment_parameter(cid)
+    return m
 
 
 def create_opt_model_clone(src_model, with_catchment_params=False):
     """expose.h:447-458: an opt (discharge-collector) model with a deep copy of src's cells, state and env."""
-    m = PTGSKOptModel(src_model)
-    if not with_catchment_params:
-        for cid in list(m._catchment_parameters):
-            m.remove_catchment_parameter(cid)
-    return m
+    return _without_catchment_params(_opt_clone(src_model), with_catchment_params)
 
 
 def create_full_model_clone(src_model, with_catchment_params=False):
-    m = PTGSKModel(src_model)
-    if not with_catchment_params:
-        for cid in list(m._catchment_parameters):
-            m.remove_catchment_parameter(cid)
-    return m
-
-
-# the model types know their optimizer, parameter and state types (expose.h:147-170, model_calibrator)
-from .._calibration import make_optimizer_type  # noqa: E402
-
-PTGSKOptimizer = make_optimizer_type("PTGSKOptimizer", _api._PTGSKOptimizer)
-for _m in (PTGSKModel, PTGSKOptModel):
-    _m.optimizer_t = PTGSKOptimizer
-    _m.parameter_t = _PTGSKBase._parameter_t
-    _m.state_t = _PTGSKBase._state_t
-del _m
+    return _without_catchment_params(_full_clone(src_model), with_catchment_params)

@@ -2,8 +2,8 @@
 shyft/api/pt_hps_k/__init__.py) over the MI355X engine."""
 from __future__ import annotations
 
-from .. import (_api, _FlatParameter, _FlatState, _ModelMixin, _Statistics, _Vector, SERIES_STATE,
-                make_state_with_id_types)
+from .. import (_api, _FlatState, _make_models, _ModelMixin, _SnowDistributionParameter, _Statistics, _Vector,
+                SERIES_STATE, make_state_with_id_types)
 
 # get/set order and names (core/pt_hps_k.h:64-159); defaults (kirchner.h:120-125, hbv_physical_snow.h:41-57,
 # glacier_melt.h:28-32, routing.h:76, mstack_param.h). gm.direct_response is a member but not a calibration value
@@ -19,16 +19,11 @@ _DEFAULTS = (-2.439, 0.966, -0.10, 1.5, 0.1, 0.0, 0.5, 2.0, 1.0, 30.0, 0.9, 0.6,
 MAX_BINS = 8
 
 
-class PTHPSKParameter(_FlatParameter):
+class PTHPSKParameter(_SnowDistributionParameter):
     NAMES = _NAMES
     DEFAULTS = _DEFAULTS
     ERROR = "pt_ss_k parameter accessor: .set size missmatch"  # the reference's text (pt_hps_k.h:70)
-
-    def __init__(self, *a):
-        super().__init__(*a)
-        src = a[0] if a and isinstance(a[0], PTHPSKParameter) else None
-        self.snow_s = list(src.snow_s) if src else [1.0] * 5
-        self.snow_intervals = list(src.snow_intervals) if src else [0.0, 0.25, 0.5, 0.75, 1.0]
+    SNOW_MODEL = "hbv_physical_snow"
 
     def size(self):
         return 24
@@ -37,18 +32,6 @@ class PTHPSKParameter(_FlatParameter):
         if not 0 <= i < self.size():
             raise RuntimeError("pt_hps_k parameter accessor:.get_name(i) Out of range.")
         return self.NAMES[i]
-
-    def to_vector(self):
-        nb = len(self.snow_s)
-        if not 2 <= nb <= MAX_BINS or len(self.snow_intervals) != nb:
-            raise RuntimeError(f"hbv_physical_snow: number of snow bins must be in [2, {MAX_BINS}]")
-        x, f = self.snow_intervals, self.snow_s  # normalize_snow_distribution (hbv_physical_snow.h:71-74)
-        area = 0.0
-        for k in range(nb - 1):
-            area += 0.5 * (f[k] + f[k + 1]) * (x[k + 1] - x[k])
-        s = [v / area for v in f] + [0.0] * (MAX_BINS - nb)
-        i = list(self.snow_intervals) + [0.0] * (MAX_BINS - nb)
-        return list(self._v) + [float(nb)] + s + i
 
 
 _B = range(MAX_BINS)
@@ -86,11 +69,6 @@ class _PTHPSKBase(_ModelMixin):
     _SERIES = _SERIES
     _STATE_SERIES = _STATE_SERIES
 
-    def _push_parameters(self):
-        self._set_region_parameter(self._region_parameter.to_vector())
-        for cid, p in self._catchment_parameters.items():
-            self._update_catchment_parameter(cid, p.to_vector())
-
     @property
     def hbv_physical_snow_state(self):  # hbv_physical_snow_cell_state_statistics (expose_statistics.h:335-360)
         return _Statistics(self, {"swe": (SERIES_STATE + 2, True), "sca": (SERIES_STATE + 1, True),
@@ -114,49 +92,7 @@ class _PTHPSKBase(_ModelMixin):
         return _Statistics(self, {"output": (6, True), "pot_ratio": ("pot_ratio", True)})
 
 
-def _ctor(self, full, args, devices=None, shard_flags=0):
-    base = _api._PTHPSKRegionModel
-    if len(args) == 1 and isinstance(args[0], base):
-        other = args[0]
-        base.__init__(self, other, full)
-        self._region_parameter = PTHPSKParameter(other._region_parameter)
-        self._catchment_parameters = {k: PTHPSKParameter(v) for k, v in other._catchment_parameters.items()}
-        self._ip, self._env = other._ip, other._env
-        return
-    geo, region_param = args[0], args[1]
-    cps = args[2] if len(args) > 2 else {}
-    base.__init__(self, list(geo), region_param.to_vector(), {int(k): v.to_vector() for k, v in cps.items()}, full,
-                  [int(d) for d in (devices or [])], int(shard_flags))
-    self._init_python(region_param, cps)
-
-
-class PTHPSKModel(_PTHPSKBase, _api._PTHPSKRegionModel):
-    """region_model<pt_hps_k cell_complete_response_t> (pt_hps_k.cpp models())."""
-
-    def __init__(self, *args, devices=None, shard_flags=0):
-        _ctor(self, True, args, devices, shard_flags)
-
-
-class PTHPSKOptModel(_PTHPSKBase, _api._PTHPSKRegionModel):
-    """region_model<pt_hps_k cell_discharge_response_t> (pt_hps_k.cpp models())."""
-
-    def __init__(self, *args, devices=None, shard_flags=0):
-        _ctor(self, False, args, devices, shard_flags)
-
-
-def create_opt_model_clone(src_model):
-    return PTHPSKOptModel(src_model)
-
-
-def create_full_model_clone(src_model):
-    return PTHPSKModel(src_model)
-
-
-from .._calibration import make_optimizer_type  # noqa: E402
-
-PTHPSKOptimizer = make_optimizer_type("PTHPSKOptimizer", _api._PTHPSKOptimizer)
-for _m in (PTHPSKModel, PTHPSKOptModel):
-    _m.optimizer_t = PTHPSKOptimizer
-    _m.parameter_t = _PTHPSKBase._parameter_t
-    _m.state_t = _PTHPSKBase._state_t
-del _m
+PTHPSKModel, PTHPSKOptModel, create_opt_model_clone, create_full_model_clone, PTHPSKOptimizer = _make_models(
+    "PTHPSK", _PTHPSKBase, _api._PTHPSKRegionModel, _api._PTHPSKOptimizer,
+    ("region_model<pt_hps_k cell_complete_response_t> (pt_hps_k.cpp models()).",
+     "region_model<pt_hps_k cell_discharge_response_t> (pt_hps_k.cpp models())."))

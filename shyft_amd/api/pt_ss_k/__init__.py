@@ -2,8 +2,8 @@
 shyft/api/pt_ss_k/__init__.py) over the MI355X engine."""
 from __future__ import annotations
 
-from .. import (_api, _FlatParameter, _FlatState, _ModelMixin, _Statistics, _Vector, SERIES_STATE,
-                make_state_with_id_types)
+from .. import (_api, _FlatParameter, _FlatState, _make_models, _ModelMixin, _Statistics, _Vector,
+                SERIES_STATE, make_state_with_id_types)
 
 # get/set order and names (core/pt_ss_k.h:78-150); defaults of the member structs (skaugen.h:89-112,
 # kirchner.h:120-125, priestley_taylor.h, routing.h:76, mstack_param.h)
@@ -74,50 +74,7 @@ class _PTSSKBase(_ModelMixin):
         return _Statistics(self, {"output": (6, True), "pot_ratio": ("pot_ratio", True)})
 
 
-def _ctor(self, full, args, devices=None, shard_flags=0):
-    base = _api._PTSSKRegionModel
-    if len(args) == 1 and isinstance(args[0], base):
-        other = args[0]
-        base.__init__(self, other, full)
-        self._region_parameter = PTSSKParameter(other._region_parameter)
-        self._catchment_parameters = {k: PTSSKParameter(v) for k, v in other._catchment_parameters.items()}
-        self._ip, self._env = other._ip, other._env  # the reference shares region_env (region_model.h:446-448)
-        return
-    geo, region_param = args[0], args[1]
-    cps = args[2] if len(args) > 2 else {}
-    base.__init__(self, list(geo), region_param.to_vector(), {int(k): v.to_vector() for k, v in cps.items()}, full,
-                  [int(d) for d in (devices or [])], int(shard_flags))
-    self._init_python(region_param, cps)
-
-
-class PTSSKModel(_PTSSKBase, _api._PTSSKRegionModel):
-    """region_model<pt_ss_k cell_complete_response_t> (pt_ss_k.cpp:139)."""
-
-    def __init__(self, *args, devices=None, shard_flags=0):
-        _ctor(self, True, args, devices, shard_flags)
-
-
-class PTSSKOptModel(_PTSSKBase, _api._PTSSKRegionModel):
-    """region_model<pt_ss_k cell_discharge_response_t> (pt_ss_k.cpp:140)."""
-
-    def __init__(self, *args, devices=None, shard_flags=0):
-        _ctor(self, False, args, devices, shard_flags)
-
-
-def create_opt_model_clone(src_model):
-    return PTSSKOptModel(src_model)
-
-
-def create_full_model_clone(src_model):
-    return PTSSKModel(src_model)
-
-
-# the model types know their optimizer, parameter and state types (expose.h:147-170, model_calibrator)
-from .._calibration import make_optimizer_type  # noqa: E402
-
-PTSSKOptimizer = make_optimizer_type("PTSSKOptimizer", _api._PTSSKOptimizer)
-for _m in (PTSSKModel, PTSSKOptModel):
-    _m.optimizer_t = PTSSKOptimizer
-    _m.parameter_t = _PTSSKBase._parameter_t
-    _m.state_t = _PTSSKBase._state_t
-del _m
+PTSSKModel, PTSSKOptModel, create_opt_model_clone, create_full_model_clone, PTSSKOptimizer = _make_models(
+    "PTSSK", _PTSSKBase, _api._PTSSKRegionModel, _api._PTSSKOptimizer,
+    ("region_model<pt_ss_k cell_complete_response_t> (pt_ss_k.cpp:139).",
+     "region_model<pt_ss_k cell_discharge_response_t> (pt_ss_k.cpp:140)."))

@@ -85,7 +85,8 @@ struct ptssk_kargs {
     const uint8_t* active;   // [N] or null
     int32_t* err;            // [N]
     int uniform_params;      // 1: every cell uses parameter set 0 (n_sets == 1)
-    int nb_max;              // pt_hs_k: the largest snow bin count of the parameter sets
+    int nb_max;              // the largest snow bin count of the parameter sets (pt_ss_k, without bins: HBV_MAX_BINS);
+                             // pt_hs_k picks its kernel instance by it
 };
 
 hipError_t launch_ptssk_run(const ptssk_kargs& a, hipStream_t stream);

@@ -12,6 +12,7 @@
 #include "../../../include/shyft_hip.h"
 #include "kernels.h"
 #include "layout.h"
+#include "stack_desc.h"
 
 namespace shyft_hip_impl {
 
@@ -58,6 +59,7 @@ struct shyft_hip_region {
     // every entry point forwards to shards.hip
     shyft_hip_impl::shard_set* sh = nullptr;
     int stack = 0;
+    const stack_desc* sd = nullptr;  // the stack's row of STACK_TABLE, set with `stack` at create and clone
     size_t n = 0;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -152,25 +154,14 @@ struct shyft_hip_region {
     bool pthsk() const { return stack == SHYFT_HIP_PT_HS_K; }
     bool pthpsk() const { return stack == SHYFT_HIP_PT_HPS_K; }
     size_t n_series() const {
-        if (collect == COLLECT_ALL) return hbv() ? HBV_NR : PTGSK_NR;
+        if (collect == COLLECT_ALL) return sd->n_full_series;
         return collect == COLLECT_DISCHARGE_SNOW ? 4 : 2;
     }
-    size_t n_state_fields() const {
-        return hbv() ? HBV_NS : (ptssk() ? PTSSK_NS : (pthsk() ? PTHSK_NS : (pthpsk() ? PTHPSK_NS : PTGSK_NS)));
-    }
-    // state-collector series per cell (pt_ss_k collects 7 series from its 8 state values)
-    size_t n_state_series() const {
-        return ptssk() ? PTSSK_NSC : (pthsk() ? PTHSK_NSC : (pthpsk() ? PTHPSK_NSC : n_state_fields()));
-    }
-    size_t n_ref_params() const {
-        return hbv() ? HBV_NP_REF
-                     : (ptssk() ? PTSSK_NP : (pthsk() ? PTHSK_NP_REF : (pthpsk() ? PTHPSK_NP_REF : PTGSK_NP_REF)));
-    }
-    size_t param_width() const {
-        return hbv() ? HBV_NP : (ptssk() ? PTSSK_NP : (pthsk() ? PTHSK_NP : (pthpsk() ? PTHPSK_NP : PTGSK_NP_REF)));
-    }
-    // hbv_snow quantile distribution (n_bins, s[], intervals[]) in the parameter row, or -1
-    int snow_dist_index() const { return hbv() ? HK_NB : (pthsk() ? PH_NB : (pthpsk() ? PP_NB : -1)); }
+    size_t n_state_fields() const { return sd->n_state_fields; }
+    size_t n_state_series() const { return sd->n_state_series; }
+    size_t n_ref_params() const { return sd->n_ref_params; }
+    size_t param_width() const { return sd->param_width; }
+    int snow_dist_index() const { return sd->snow_dist_index; }
 };
 
 namespace shyft_hip_impl {

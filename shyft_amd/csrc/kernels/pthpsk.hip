@@ -15,8 +15,7 @@
 
 #include "../device/stream.h"
 #include "../device/hps_dev.h"
-#include "../device/pt_dev.h"
-#include "../device/ptgsk_dev.h"
+#include "../device/pt_k_tail.h"
 #include "../include_internal/kernels.h"
 
 using namespace shyft_dev;
@@ -77,11 +76,10 @@ void pthpsk_run_kernel(const pthpsk_kargs a) {
         hp.fast_decay = dpow(2.0, -dt_in_days / P[PP_FAST_DECAY_RATE]);
         hp.BB0 = 0.98 * 5.670373e-8 * dpow(273.15, 4.0);
     }
-    const double kc1 = P[PP_C1], kc2 = P[PP_C2], kc3 = P[PP_C3];
-    const double ae_scale = P[PP_AE_SCALE], p_corr = P[PP_PCORR], dtf = P[PP_DTF];
-    const double pt_albedo = P[PP_PT_ALBEDO], pt_alpha = P[PP_PT_ALPHA];
+    const double p_corr = P[PP_PCORR];
     const double gm_direct = P[PP_GM_DIRECT];
-    const double gm_routed = 1 - gm_direct;
+    const pt_k_tail_par tp{P[PP_C1], P[PP_C2], P[PP_C3], P[PP_AE_SCALE], P[PP_DTF], P[PP_PT_ALBEDO], P[PP_PT_ALPHA],
+                           gm_direct, 1 - gm_direct};
 
     const double* __restrict__ cc = a.cellc;  // pt_hps_k.h:233-242 (same rows as pt_gs_k)
     const double glacier_fraction = cc[PC_GLACIER * N + cell];
@@ -170,36 +168,22 @@ void pthpsk_run_kernel(const pthpsk_kargs a) {
         double r_sca, r_storage;
         const double snow_outflow = hps_step(hp, sp, sw, alb, iso, swe, sca, surface_heat, dt_us, dts, temp, rad, prec,
                                              wind_speed, rel_hum, r_sca, r_storage, err);
-        const double sca_area = cell_area_m2 * sca;
-        double gm_melt_m3s = 0.0;
-        if (!(glacier_area_m2 <= sca_area || temp <= 0.0))
-            gm_melt_m3s = dtf * temp * (glacier_area_m2 - sca_area) * (0.001 / 86400.0);
-        double ae_exp;  // actual_evapotranspiration's exp, evaluated beside Priestley-Taylor's (pt_pot_evap_exp)
-        const double pot_evap = pt_pot_evap_exp<true>(pt_albedo, pt_alpha, temp, rad, rel_hum, -q * 3.0 / ae_scale, ae_exp) * 3600.0;
-        const double ae = pot_evap * (1.0 - ae_exp) * (1.0 - smax(sca, glacier_fraction));
-        const double gm_mmh = gm_melt_m3s / (mmh_to_m3s_scale_factor * cell_area_m2);
-        double q_avg;
-        if (!kirchner_step<true>(q, q_avg, snow_outflow * snow_storage_fraction + prec * kirchner_routed_prec + gm_routed * gm_mmh,
-                           ae, a.t1_hours, kc1, kc2, kc3))
-            err = ERR_KIRCHNER_MAX_ITER;
-        const double total_discharge = smax(0.0, prec - ae) * direct_response_fraction + gm_direct * gm_mmh +
-                                       q_avg * kirchner_fraction;
-        const double charge_m3s = +(cell_area_m2 * prec * mmh_to_m3s_scale_factor) -
-                                  (cell_area_m2 * ae * mmh_to_m3s_scale_factor) + gm_melt_m3s -
-                                  (cell_area_m2 * total_discharge * mmh_to_m3s_scale_factor);
+        const pt_k_tail_out o = pt_k_tail<true>(
+            tp, glacier_fraction, snow_storage_fraction, kirchner_routed_prec, direct_response_fraction, kirchner_fraction,
+            cell_area_m2, glacier_area_m2, a.t1_hours, temp, rad, rel_hum, prec, sca, snow_outflow, q, err);
         // all_response_collector of response.scale_snow(snow_storage_fraction) (pt_hps_k_cell_model.h:82-91,
         // pt_hps_k.h:196-202): hps_outflow is collected in mm/h, as the reference does
-        stream_st<STREAM_NT>(&R[PR_AVG_DISCHARGE * RS + fo], cell_area_m2 * total_discharge * mmh_to_m3s_scale_factor);
-        stream_st<STREAM_NT>(&R[PR_CHARGE_M3S * RS + fo], charge_m3s);
+        stream_st<STREAM_NT>(&R[PR_AVG_DISCHARGE * RS + fo], o.discharge_m3s);
+        stream_st<STREAM_NT>(&R[PR_CHARGE_M3S * RS + fo], o.charge_m3s);
         if (a.collect >= 1) {
             R[PR_SNOW_SCA * RS + fo] = r_sca;
             R[PR_SNOW_SWE * RS + fo] = r_storage * snow_storage_fraction;
         }
         if (a.collect >= 2) {
             R[PR_SNOW_OUTFLOW * RS + fo] = snow_outflow * snow_storage_fraction;
-            R[PR_GLACIER_MELT * RS + fo] = gm_melt_m3s;
-            R[PR_AE_OUTPUT * RS + fo] = ae;
-            R[PR_PE_OUTPUT * RS + fo] = pot_evap;
+            R[PR_GLACIER_MELT * RS + fo] = o.gm_melt_m3s;
+            R[PR_AE_OUTPUT * RS + fo] = o.ae;
+            R[PR_PE_OUTPUT * RS + fo] = o.pot_evap;
         }
         if (SS && i + 1 == i_end) collect_state(wi + 1);
     }

@@ -18,8 +18,7 @@
 
 #include "../device/stream.h"
 #include "../device/hbv_dev.h"
-#include "../device/pt_dev.h"
-#include "../device/ptgsk_dev.h"
+#include "../device/pt_k_tail.h"
 #include "../include_internal/kernels.h"
 
 using namespace shyft_dev;
@@ -70,11 +69,10 @@ void pthsk_run_kernel(const pthsk_kargs a) {
     sp_par.ts = P[PH_TS];
     sp_par.lw = P[PH_LW];
     sp_par.cfr = P[PH_CFR];
-    const double kc1 = P[PH_C1], kc2 = P[PH_C2], kc3 = P[PH_C3];
-    const double ae_scale = P[PH_AE_SCALE], p_corr = P[PH_PCORR], dtf = P[PH_DTF];
-    const double pt_albedo = P[PH_PT_ALBEDO], pt_alpha = P[PH_PT_ALPHA];
+    const double p_corr = P[PH_PCORR];
     const double gm_direct = P[PH_GM_DIRECT];
-    const double gm_routed = 1 - gm_direct;
+    const pt_k_tail_par tp{P[PH_C1], P[PH_C2], P[PH_C3], P[PH_AE_SCALE], P[PH_DTF], P[PH_PT_ALBEDO], P[PH_PT_ALPHA],
+                           gm_direct, 1 - gm_direct};
 
     const double* __restrict__ cc = a.cellc;  // pt_hs_k.h:233-242 (same rows as pt_gs_k)
     const double glacier_fraction = cc[PC_GLACIER * N + cell];
@@ -140,38 +138,22 @@ void pthsk_run_kernel(const pthsk_kargs a) {
         const double prec = stream_ld<STREAM_NT>(&f_prec[ff]) * p_corr;
         if (SS) collect_state(wi);
         const double snow_outflow = hbv_snow_step(sp_par, sp, sw, swe, sca, a.step_in_days, a.dt_hours, prec, temp, err);
-        // glacier_melt::step (glacier_melt.h:47-52) on the post-step snow covered area
-        const double sca_area = cell_area_m2 * sca;
-        double gm_melt_m3s = 0.0;
-        if (!(glacier_area_m2 <= sca_area || temp <= 0.0))
-            gm_melt_m3s = dtf * temp * (glacier_area_m2 - sca_area) * (0.001 / 86400.0);
-        double ae_exp;  // actual_evapotranspiration's exp, evaluated beside Priestley-Taylor's (pt_pot_evap_exp)
-        const double pot_evap = pt_pot_evap_exp<true>(pt_albedo, pt_alpha, temp, rad, rel_hum, -q * 3.0 / ae_scale, ae_exp) * 3600.0;
-        // actual_evapotranspiration::calculate_step (actual_evapotranspiration.h:40-62)
-        const double ae = pot_evap * (1.0 - ae_exp) * (1.0 - smax(sca, glacier_fraction));
-        const double gm_mmh = gm_melt_m3s / (mmh_to_m3s_scale_factor * cell_area_m2);
-        double q_avg;
-        if (!kirchner_step<true>(q, q_avg, snow_outflow * snow_storage_fraction + prec * kirchner_routed_prec + gm_routed * gm_mmh,
-                           ae, a.t1_hours, kc1, kc2, kc3))
-            err = ERR_KIRCHNER_MAX_ITER;
-        const double total_discharge = smax(0.0, prec - ae) * direct_response_fraction + gm_direct * gm_mmh +
-                                       q_avg * kirchner_fraction;
-        const double charge_m3s = +(cell_area_m2 * prec * mmh_to_m3s_scale_factor) -
-                                  (cell_area_m2 * ae * mmh_to_m3s_scale_factor) + gm_melt_m3s -
-                                  (cell_area_m2 * total_discharge * mmh_to_m3s_scale_factor);
+        const pt_k_tail_out o = pt_k_tail<true>(
+            tp, glacier_fraction, snow_storage_fraction, kirchner_routed_prec, direct_response_fraction, kirchner_fraction,
+            cell_area_m2, glacier_area_m2, a.t1_hours, temp, rad, rel_hum, prec, sca, snow_outflow, q, err);
         // collectors of response.scale_snow(snow_storage_fraction) (pt_hs_k.h:188-194, 274-277): the response
         // carries the post-step snow state, swe and outflow scaled
-        stream_st<STREAM_NT>(&R[PR_AVG_DISCHARGE * RS + fo], cell_area_m2 * total_discharge * mmh_to_m3s_scale_factor);
-        stream_st<STREAM_NT>(&R[PR_CHARGE_M3S * RS + fo], charge_m3s);
+        stream_st<STREAM_NT>(&R[PR_AVG_DISCHARGE * RS + fo], o.discharge_m3s);
+        stream_st<STREAM_NT>(&R[PR_CHARGE_M3S * RS + fo], o.charge_m3s);
         if (a.collect >= 1) {
             R[PR_SNOW_SCA * RS + fo] = sca;
             R[PR_SNOW_SWE * RS + fo] = swe * snow_storage_fraction;
         }
         if (a.collect >= 2) {
             R[PR_SNOW_OUTFLOW * RS + fo] = cell_area_m2 * (snow_outflow * snow_storage_fraction) * mmh_to_m3s_scale_factor;
-            R[PR_GLACIER_MELT * RS + fo] = gm_melt_m3s;
-            R[PR_AE_OUTPUT * RS + fo] = ae;
-            R[PR_PE_OUTPUT * RS + fo] = pot_evap;
+            R[PR_GLACIER_MELT * RS + fo] = o.gm_melt_m3s;
+            R[PR_AE_OUTPUT * RS + fo] = o.ae;
+            R[PR_PE_OUTPUT * RS + fo] = o.pot_evap;
         }
         if (SS && i + 1 == i_end) collect_state(wi + 1);
     }

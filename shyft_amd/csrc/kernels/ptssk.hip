@@ -17,7 +17,7 @@
 
 #ifdef SHYFT_PROF
 // phase timing (profiling builds only, tools/ptssk_phases.py): per-wavefront s_memtime deltas summed over the launch;
-// [0..5] front / queue + first barrier / job compute / second barrier / ss_back + glacier / PT + AE + kirchner +
+// [0..5] front / queue + first barrier / job compute / second barrier / ss_back / glacier + PT + AE + kirchner +
 // stores, [8] solver-wavefront job cycles, [9] solver wavefront-steps, [10] job lanes of those wavefront-steps,
 // [11..15] inside a job (device/ptssk_dev.h SS_JOB_MARK): lgammas / opening evaluations / Brent + walk / bisection /
 // final cdfs
@@ -37,8 +37,7 @@ extern "C" int shyft_ptssk_prof_read(unsigned long long* out) {
     } while (0)
 #endif
 
-#include "../device/pt_dev.h"
-#include "../device/ptgsk_dev.h"
+#include "../device/pt_k_tail.h"
 #include "../device/ptssk_dev.h"
 #include "../device/stream.h"
 #include "../device/wave_place.h"
@@ -147,11 +146,10 @@ void ptssk_run_kernel(const ptssk_kargs a) {
     sp.cx = P[SK_CX];
     sp.ts = P[SK_TS];
     sp.cfr = P[SK_CFR];
-    const double kc1 = P[SK_C1], kc2 = P[SK_C2], kc3 = P[SK_C3];
-    const double ae_scale = P[SK_AE_SCALE], p_corr = P[SK_PCORR], dtf = P[SK_DTF];
-    const double pt_albedo = P[SK_PT_ALBEDO], pt_alpha = P[SK_PT_ALPHA];
+    const double p_corr = P[SK_PCORR];
     const double gm_direct = P[SK_GM_DIRECT];
-    const double gm_routed = 1 - gm_direct;
+    const pt_k_tail_par tp{P[SK_C1], P[SK_C2], P[SK_C3], P[SK_AE_SCALE], P[SK_DTF], P[SK_PT_ALBEDO], P[SK_PT_ALPHA],
+                           gm_direct, 1 - gm_direct};
 
     const double* __restrict__ cc = a.cellc;  // pt_ss_k.h:237-245 (same rows as pt_gs_k)
     __shared__ double lcc[7][BLOCK];
@@ -297,37 +295,22 @@ void ptssk_run_kernel(const ptssk_kargs a) {
         }
         if (!valid) continue;
         ss_back(sp, a.dt_hours, s, m, rel, snow_outflow, snow_sca, snow_swe);
-        // glacier_melt::step (glacier_melt.h:47-52) on the post-step snow covered area
-        const double sca_area = cell_area_m2 * s.sca;
-        double gm_melt_m3s = 0.0;
-        if (!(glacier_area_m2 <= sca_area || temp <= 0.0))
-            gm_melt_m3s = dtf * temp * (glacier_area_m2 - sca_area) * (0.001 / 86400.0);
-        PROF_MARK(4);  // ss_back + glacier
-        double ae_exp;  // actual_evapotranspiration's exp, evaluated beside Priestley-Taylor's (pt_pot_evap_exp)
-        const double pot_evap = pt_pot_evap_exp<PTSSK_INLINE_MATH>(pt_albedo, pt_alpha, temp, rad, rel_hum, -q * 3.0 / ae_scale, ae_exp) * 3600.0;
-        const double ae = pot_evap * (1.0 - ae_exp) * (1.0 - smax(s.sca, glacier_fraction));
-        const double gm_mmh = gm_melt_m3s / (mmh_to_m3s_scale_factor * cell_area_m2);
-        double q_avg;
-        if (!kirchner_step<PTSSK_INLINE_MATH>(q, q_avg, snow_outflow * snow_storage_fraction + prec * kirchner_routed_prec + gm_routed * gm_mmh,
-                           ae, a.t1_hours, kc1, kc2, kc3))
-            err = ERR_KIRCHNER_MAX_ITER;
-        const double total_discharge = smax(0.0, prec - ae) * direct_response_fraction + gm_direct * gm_mmh +
-                                       q_avg * kirchner_fraction;
-        const double charge_m3s = +(cell_area_m2 * prec * mmh_to_m3s_scale_factor) -
-                                  (cell_area_m2 * ae * mmh_to_m3s_scale_factor) + gm_melt_m3s -
-                                  (cell_area_m2 * total_discharge * mmh_to_m3s_scale_factor);
+        PROF_MARK(4);  // ss_back
+        const pt_k_tail_out o = pt_k_tail<PTSSK_INLINE_MATH>(
+            tp, glacier_fraction, snow_storage_fraction, kirchner_routed_prec, direct_response_fraction, kirchner_fraction,
+            cell_area_m2, glacier_area_m2, a.t1_hours, temp, rad, rel_hum, prec, s.sca, snow_outflow, q, err);
         // collectors of response.scale_snow(snow_storage_fraction) (pt_ss_k.h:198-203)
-        stream_st<STREAM_NT>(&R[PR_AVG_DISCHARGE * RS + fo], cell_area_m2 * total_discharge * mmh_to_m3s_scale_factor);
-        stream_st<STREAM_NT>(&R[PR_CHARGE_M3S * RS + fo], charge_m3s);
+        stream_st<STREAM_NT>(&R[PR_AVG_DISCHARGE * RS + fo], o.discharge_m3s);
+        stream_st<STREAM_NT>(&R[PR_CHARGE_M3S * RS + fo], o.charge_m3s);
         if (a.collect >= 1) {
             R[PR_SNOW_SCA * RS + fo] = snow_sca;
             R[PR_SNOW_SWE * RS + fo] = snow_swe * snow_storage_fraction;
         }
         if (a.collect >= 2) {
             R[PR_SNOW_OUTFLOW * RS + fo] = cell_area_m2 * (snow_outflow * snow_storage_fraction) * mmh_to_m3s_scale_factor;
-            R[PR_GLACIER_MELT * RS + fo] = gm_melt_m3s;
-            R[PR_AE_OUTPUT * RS + fo] = ae;
-            R[PR_PE_OUTPUT * RS + fo] = pot_evap;
+            R[PR_GLACIER_MELT * RS + fo] = o.gm_melt_m3s;
+            R[PR_AE_OUTPUT * RS + fo] = o.ae;
+            R[PR_PE_OUTPUT * RS + fo] = o.pot_evap;
         }
         if (SS && i + 1 == i_end) collect_state(wi + 1);
         PROF_MARK(5);

@@ -131,112 +131,72 @@ void update_ix_to_id_mapping(shyft_hip_region* h) {
     hip_check(region_copy(h, h->d_seg_off.p, off.data(), (C + 1) * sizeof(int32_t), hipMemcpyHostToDevice), "upload seg");
 }
 
-// derived per-set parameter rows and per-cell constants (pt_gs_k.h:347-357,
-// gamma_snow.h:85-87, :188, :340-343). Evaluated with the same expressions
-// the reference evaluates, on the host.
-void update_derived_hbv(shyft_hip_region* h) {
-    const size_t N = h->n;
-    std::vector<double> cc(HBV_NC * N);
-    for (size_t i = 0; i < N; ++i) {
-        const double* g = &h->geo[i * 11];
-        const double* p = &h->params[size_t(h->set_ix[i]) * HBV_NP];
-        const double glacier = g[6], reservoir = g[8];
-        const double direct = glacier * p[HK_GM_DIRECT] + reservoir * p[HK_RSV_DRF];
-        cc[HC_GLACIER * N + i] = glacier;
-        cc[HC_DIRECT_RESPONSE * N + i] = direct;
-        cc[HC_LAND_FRACTION * N + i] = 1 - direct;
-        cc[HC_AREA * N + i] = g[3];
-        cc[HC_GLACIER_AREA * N + i] = g[3] * glacier;
-    }
-    h->d_params.alloc(h->params.size());
-    h->d_cellc.alloc(cc.size());
-    h->d_set_ix.alloc(N);
-    hip_check(region_copy(h, h->d_params.p, h->params.data(), h->params.size() * sizeof(double), hipMemcpyHostToDevice),
-              "upload params");
-    hip_check(region_copy(h, h->d_cellc.p, cc.data(), cc.size() * sizeof(double), hipMemcpyHostToDevice), "upload cellc");
-    hip_check(region_copy(h, h->d_set_ix.p, h->set_ix.data(), N * sizeof(int32_t), hipMemcpyHostToDevice), "upload set_ix");
-    h->derived_dirty = false;
-}
-
-// pt_ss_k / pt_hs_k: parameter rows as given, per-cell constants of pt_ss_k.h:237-245 (pt_hs_k.h:233-242,
-// the same expressions) in the pt_gs_k PC_* rows
-void update_derived_ptssk(shyft_hip_region* h) {
-    const size_t N = h->n;
-    const size_t width = h->param_width();
-    const int k_gm = h->pthsk() ? PH_GM_DIRECT : (h->pthpsk() ? PP_GM_DIRECT : SK_GM_DIRECT);
-    const int k_rsv = h->pthsk() ? PH_RSV_DRF : (h->pthpsk() ? PP_RSV_DRF : SK_RSV_DRF);
-    std::vector<double> cc(PTGSK_NC * N, 0.0);
-    for (size_t i = 0; i < N; ++i) {
-        const double* g = &h->geo[i * 11];
-        const double* p = &h->params[size_t(h->set_ix[i]) * width];
-        const double glacier = g[6], lake = g[7], reservoir = g[8];
-        const double gm_direct = p[k_gm];
-        const double rdrf = p[k_rsv];
-        const double direct = glacier * gm_direct + reservoir * rdrf;
-        cc[PC_GLACIER * N + i] = glacier;
-        cc[PC_SNOW_STORAGE * N + i] = 1.0 - lake - reservoir;
-        cc[PC_KIRCHNER_ROUTED_PREC * N + i] = reservoir * (1.0 - rdrf) + lake;
-        cc[PC_DIRECT_RESPONSE * N + i] = direct;
-        cc[PC_KIRCHNER_FRACTION * N + i] = 1 - direct;
-        cc[PC_AREA * N + i] = g[3];
-        cc[PC_GLACIER_AREA * N + i] = g[3] * glacier;
-    }
-    h->d_params.alloc(h->params.size());
-    h->d_cellc.alloc(cc.size());
-    h->d_set_ix.alloc(N);
-    hip_check(region_copy(h, h->d_params.p, h->params.data(), h->params.size() * sizeof(double), hipMemcpyHostToDevice),
-              "upload params");
-    hip_check(region_copy(h, h->d_cellc.p, cc.data(), cc.size() * sizeof(double), hipMemcpyHostToDevice), "upload cellc");
-    hip_check(region_copy(h, h->d_set_ix.p, h->set_ix.data(), N * sizeof(int32_t), hipMemcpyHostToDevice), "upload set_ix");
-    h->derived_dirty = false;
-}
-
+// derived per-set parameter rows and per-cell constants (pt_gs_k.h:347-357, gamma_snow.h:85-87, :188, :340-343;
+// pt_ss_k.h:237-245, pt_hs_k.h:233-242 and hbv_stack.h:311-318 are the same expressions). Evaluated with the same
+// expressions the reference evaluates, on the host. The PT stacks share the pt_gs_k PC_* rows (the rows only
+// pt_gs_k fills stay 0); hbv_stack has its own, shorter HC_* rows.
 void update_derived(shyft_hip_region* h) {
     if (!h->derived_dirty) return;
     if (!h->has_geo) throw std::runtime_error("region: geo_cell_data not set");
     if (!h->has_params) throw std::runtime_error("region: parameters not set");
     if (h->dt <= 0) throw std::runtime_error("region_model::run with invalid time_axis invoked");
-    if (h->hbv()) return update_derived_hbv(h);
-    if (h->ptssk() || h->pthsk() || h->pthpsk()) return update_derived_ptssk(h);
+    const stack_desc& sd = *h->sd;
+    const bool ptgsk = sd.id == SHYFT_HIP_PT_GS_K;
     const size_t N = h->n;
-    const double dt_s = double(h->dt) / 1e6;
-    const double dt_in_days = dt_s / 86400.0;
-    std::vector<double> P(h->n_sets * PTGSK_NP, 0.0);
-    for (size_t k = 0; k < h->n_sets; ++k) {
-        const double* p = &h->params[k * PTGSK_NP_REF];
-        double* q = &P[k * PTGSK_NP];
-        for (int j = 0; j < PTGSK_NP_REF; ++j) q[j] = p[j];
-        q[PK_WED] = double(size_t(p[PK_WED]));   // size_t(p[i]) (pt_gs_k.h:103)
-        q[PK_NWD] = double(size_t(p[PK_NWD]));   // implicit size_t conversion (pt_gs_k.h:109)
-        q[PK_ISO] = p[PK_ISO] != 0.0 ? 1.0 : 0.0;
-        const double albedo_range = p[PK_MAX_ALBEDO] - p[PK_MIN_ALBEDO];
-        q[PK_ALBEDO_RANGE] = albedo_range;
-        q[PK_SLOW_DECAY] = 0.5 * albedo_range * dt_in_days / p[PK_SLOW_DECAY_RATE];
-        q[PK_FAST_DECAY] = detmath::pow(2.0, -dt_in_days / p[PK_FAST_DECAY_RATE]);
-        q[PK_BB0] = 0.98 * 5.670373e-8 * detmath::pow(273.15, 4.0);
-        q[PK_INV_CV2_PARAM] = 1.0 / (p[PK_SNOW_CV] * p[PK_SNOW_CV]);
-    }
-    std::vector<double> cc(PTGSK_NC * N);
+    const size_t width = sd.param_width;
+    std::vector<double> cc(size_t(sd.n_cellc) * N, 0.0);
     for (size_t i = 0; i < N; ++i) {
         const double* g = &h->geo[i * 11];
-        const double* p = &h->params[size_t(h->set_ix[i]) * PTGSK_NP_REF];
-        const double glacier = g[6], lake = g[7], reservoir = g[8], forest = g[9];
-        const double gm_direct = p[PK_GM_DIRECT];
-        const double rdrf = p[PK_RSV_DRF];
+        const double* p = &h->params[size_t(h->set_ix[i]) * width];
+        const double glacier = g[6], lake = g[7], reservoir = g[8];
+        const double gm_direct = p[sd.k_gm_direct];
+        const double rdrf = p[sd.k_rsv_drf];
         const double direct = glacier * gm_direct + reservoir * rdrf;
-        const double cv = p[PK_SNOW_CV] + forest * p[PK_CV_FOREST] + g[2] * p[PK_CV_ALT];
-        cc[PC_FOREST * N + i] = forest;
-        cc[PC_GLACIER * N + i] = glacier;
-        cc[PC_SNOW_STORAGE * N + i] = 1.0 - lake - reservoir;
-        cc[PC_KIRCHNER_ROUTED_PREC * N + i] = reservoir * (1.0 - rdrf) + lake;
-        cc[PC_DIRECT_RESPONSE * N + i] = direct;
-        cc[PC_KIRCHNER_FRACTION * N + i] = 1 - direct;
-        cc[PC_AREA * N + i] = g[3];
-        cc[PC_GLACIER_AREA * N + i] = g[3] * glacier;
-        cc[PC_ALTITUDE * N + i] = g[2];
-        cc[PC_CV2 * N + i] = cv * cv;
-        cc[PC_INV_CV2 * N + i] = 1.0 / (cv * cv);
+        if (h->hbv()) {
+            cc[HC_GLACIER * N + i] = glacier;
+            cc[HC_DIRECT_RESPONSE * N + i] = direct;
+            cc[HC_LAND_FRACTION * N + i] = 1 - direct;
+            cc[HC_GLACIER_AREA * N + i] = g[3] * glacier;
+        } else {
+            cc[PC_GLACIER * N + i] = glacier;
+            cc[PC_SNOW_STORAGE * N + i] = 1.0 - lake - reservoir;
+            cc[PC_KIRCHNER_ROUTED_PREC * N + i] = reservoir * (1.0 - rdrf) + lake;
+            cc[PC_DIRECT_RESPONSE * N + i] = direct;
+            cc[PC_KIRCHNER_FRACTION * N + i] = 1 - direct;
+            cc[PC_GLACIER_AREA * N + i] = g[3] * glacier;
+        }
+        cc[sd.c_area * N + i] = g[3];
+        if (ptgsk) {
+            const double forest = g[9];
+            const double cv = p[PK_SNOW_CV] + forest * p[PK_CV_FOREST] + g[2] * p[PK_CV_ALT];
+            cc[PC_FOREST * N + i] = forest;
+            cc[PC_ALTITUDE * N + i] = g[2];
+            cc[PC_CV2 * N + i] = cv * cv;
+            cc[PC_INV_CV2 * N + i] = 1.0 / (cv * cv);
+        }
     }
+    // the device rows: as given, but pt_gs_k's with the columns derived for this run's dt behind them
+    std::vector<double> derived;
+    if (ptgsk) {
+        const double dt_s = double(h->dt) / 1e6;
+        const double dt_in_days = dt_s / 86400.0;
+        derived.assign(h->n_sets * PTGSK_NP, 0.0);
+        for (size_t k = 0; k < h->n_sets; ++k) {
+            const double* p = &h->params[k * PTGSK_NP_REF];
+            double* q = &derived[k * PTGSK_NP];
+            for (int j = 0; j < PTGSK_NP_REF; ++j) q[j] = p[j];
+            q[PK_WED] = double(size_t(p[PK_WED]));   // size_t(p[i]) (pt_gs_k.h:103)
+            q[PK_NWD] = double(size_t(p[PK_NWD]));   // implicit size_t conversion (pt_gs_k.h:109)
+            q[PK_ISO] = p[PK_ISO] != 0.0 ? 1.0 : 0.0;
+            const double albedo_range = p[PK_MAX_ALBEDO] - p[PK_MIN_ALBEDO];
+            q[PK_ALBEDO_RANGE] = albedo_range;
+            q[PK_SLOW_DECAY] = 0.5 * albedo_range * dt_in_days / p[PK_SLOW_DECAY_RATE];
+            q[PK_FAST_DECAY] = detmath::pow(2.0, -dt_in_days / p[PK_FAST_DECAY_RATE]);
+            q[PK_BB0] = 0.98 * 5.670373e-8 * detmath::pow(273.15, 4.0);
+            q[PK_INV_CV2_PARAM] = 1.0 / (p[PK_SNOW_CV] * p[PK_SNOW_CV]);
+        }
+    }
+    const std::vector<double>& P = ptgsk ? derived : h->params;
     h->d_params.alloc(P.size());
     h->d_cellc.alloc(cc.size());
     h->d_set_ix.alloc(N);
@@ -343,6 +303,30 @@ void clone_buf(dbuf<T>& dst, const dbuf<T>& src) {
     hip_check(hipMemcpy(dst.p, src.p, src.n * sizeof(T), hipMemcpyDeviceToDevice), "clone");
 }
 
+// the run-kernel arguments every stack has, steps [b, e)
+template <class A>
+void fill_common(A& a, const shyft_hip_region* h, size_t b, size_t e) {
+    a.n_cells = int(h->n);
+    a.step0 = int(b);
+    a.n_steps = int(e - b);
+    a.win0 = int(h->w0);
+    a.win_len = int(h->TW);
+    a.collect = h->collect;
+    a.params = h->d_params.p;
+    a.set_ix = h->d_set_ix.p;
+    a.cellc = h->d_cellc.p;
+    a.state = h->d_state.p;
+    // an ensemble lane region reads its parent's forcing, each lane the column of its cell
+    a.forcing = h->forcing_src ? h->forcing_src->d_forcing.p : h->d_forcing.p;
+    a.fcol = h->forcing_src ? h->d_fcol.p : nullptr;
+    a.f_cols = int(h->forcing_src ? h->forcing_src->n : h->n);
+    a.resp = h->d_resp.p;
+    a.state_series = h->collect_state ? h->d_state_series.p : nullptr;
+    a.active = h->active.empty() ? nullptr : h->d_active.p;
+    a.err = h->d_err.p;
+    a.uniform_params = h->n_sets == 1 ? 1 : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -352,12 +336,12 @@ const char* shyft_hip_last_error(const shyft_hip_region* h) { return h ? h->err.
 int shyft_hip_region_create(int stack, size_t n_cells, int device, shyft_hip_region** out) {
     if (!out) return fail(nullptr, "shyft_hip_region_create: out is null");
     *out = nullptr;
-    if (stack != SHYFT_HIP_PT_GS_K && stack != SHYFT_HIP_HBV_STACK && stack != SHYFT_HIP_PT_SS_K &&
-        stack != SHYFT_HIP_PT_HS_K && stack != SHYFT_HIP_PT_HPS_K)
-        return fail(nullptr, "shyft_hip_region_create: unsupported method stack");
+    const stack_desc* sd = stack_desc_of(stack);
+    if (!sd) return fail(nullptr, "shyft_hip_region_create: unsupported method stack");
     if (n_cells == 0 || n_cells > (size_t)INT32_MAX) return fail(nullptr, "shyft_hip_region_create: invalid n_cells");
     std::unique_ptr<shyft_hip_region> h(new shyft_hip_region());
     h->stack = stack;
+    h->sd = sd;
     h->n = n_cells;
     try {
         if (device < 0) hip_check(hipGetDevice(&device), "hipGetDevice");
@@ -392,13 +376,13 @@ int shyft_hip_region_create_sharded_ex(int stack, size_t n_cells, const int* dev
                                        shyft_hip_region** out) {
     if (!out) return fail(nullptr, "shyft_hip_region_create_sharded: out is null");
     *out = nullptr;
-    if (stack != SHYFT_HIP_PT_GS_K && stack != SHYFT_HIP_HBV_STACK && stack != SHYFT_HIP_PT_SS_K &&
-        stack != SHYFT_HIP_PT_HS_K && stack != SHYFT_HIP_PT_HPS_K)
-        return fail(nullptr, "shyft_hip_region_create: unsupported method stack");
+    const stack_desc* sd = stack_desc_of(stack);
+    if (!sd) return fail(nullptr, "shyft_hip_region_create: unsupported method stack");
     if (n_cells == 0 || n_cells > (size_t)INT32_MAX) return fail(nullptr, "shyft_hip_region_create: invalid n_cells");
     try {
         std::unique_ptr<shyft_hip_region> h(new shyft_hip_region());
         h->stack = stack;
+        h->sd = sd;
         h->n = n_cells;
         h->device = devices && n_shards ? devices[0] : 0;
         h->sh = shard_set_create(stack, n_cells, devices, n_shards, flags);
@@ -485,20 +469,9 @@ int shyft_hip_set_parameters(shyft_hip_region* h, const double* params, size_t n
     if (h->sh) return guarded(h, [&] { shards::set_parameters(h->sh, params, n_sets, n_per_set, set_ix); });
     return guarded(h, [&] {
         const size_t width = h->param_width();
-        if (h->hbv()) {
-            if (n_per_set != HBV_NP_REF && n_per_set != HBV_NP)
-                throw std::runtime_error("HBV_Stack Parameter Accessor: .set size missmatch");
-        } else if (h->ptssk()) {
-            if (n_per_set != PTSSK_NP) throw std::runtime_error("pt_ss_k parameter accessor: .set size mismatch");
-        } else if (h->pthsk()) {
-            if (n_per_set != PTHSK_NP_REF && n_per_set != PTHSK_NP)
-                throw std::runtime_error("pt_ss_k parameter accessor: .set size missmatch");  // pt_hs_k.h:68 text
-        } else if (h->pthpsk()) {
-            if (n_per_set != PTHPSK_NP_REF && n_per_set != PTHPSK_NP)
-                throw std::runtime_error("pt_ss_k parameter accessor: .set size missmatch");  // pt_hps_k.h:70 text
-        } else if (n_per_set != h->n_ref_params()) {
-            throw std::runtime_error("PTGSK Parameter Accessor: .set size missmatch");
-        }
+        // the reference's row, or this library's row with the snow distribution behind it
+        if (n_per_set != h->n_ref_params() && !(h->snow_dist_index() >= 0 && n_per_set == width))
+            throw std::runtime_error(h->sd->param_error);
         if (n_sets == 0) throw std::runtime_error("shyft_hip_set_parameters: n_sets == 0");
         std::vector<int32_t> ix(h->n, 0);
         if (set_ix) {
@@ -512,7 +485,7 @@ int shyft_hip_set_parameters(shyft_hip_region* h, const double* params, size_t n
         for (size_t k = 0; k < n_sets; ++k) {
             double* q = &h->params[k * width];
             for (size_t j = 0; j < n_per_set; ++j) q[j] = params[k * n_per_set + j];
-            const int kd = h->snow_dist_index();  // HK_NB / PH_NB: n_bins, s[HBV_MAX_BINS], intervals[HBV_MAX_BINS]
+            const int kd = h->snow_dist_index();  // n_bins, s[HBV_MAX_BINS], intervals[HBV_MAX_BINS]
             if (kd >= 0 && n_per_set == h->n_ref_params()) {
                 // hbv_snow::parameter() default distribution: s = 1 (normalised mean of ones is exactly 1),
                 // quantiles 0, .25, .5, .75, 1 (hbv_snow.h:29-41)
@@ -1150,115 +1123,52 @@ static void launch_run(shyft_hip_region* h, int start_step, int n_steps) {
     size_t b = n_steps > 0 ? size_t(start_step) : 0;
     size_t e = n_steps > 0 ? size_t(start_step + n_steps) : h->T;
     check_window(h, b, e - b, "run_cells");
+    const double dt_s = double(h->dt) / 1e6;  // to_seconds(period.timespan())
+    // the largest snow bin count of the parameter sets (the kernels with bins in registers pick their instance by it)
+    int nb_max = HBV_MAX_BINS;
+    if (const int kd = h->snow_dist_index(); kd >= 0) {
+        nb_max = 0;
+        for (size_t k = 0; k < h->n_sets; ++k) nb_max = std::max(nb_max, int(h->params[k * h->param_width() + kd]));
+    }
+    hip_check(hipEventRecord(h->ev0, h->stream), "hipEventRecord");
     if (h->ptssk() || h->pthsk() || h->pthpsk()) {
         ptssk_kargs a;
-        a.n_cells = int(h->n);
-        a.step0 = int(b);
-        a.n_steps = int(e - b);
-        a.win0 = int(h->w0);
-        a.win_len = int(h->TW);
-        a.collect = h->collect;
-        const double dt_s = double(h->dt) / 1e6;  // to_seconds(period.timespan())
+        fill_common(a, h, b, e);
         a.step_in_days = dt_s / 86400.0;
         a.dt_hours = dt_s / 3600.0;
         a.t1_hours = dt_s / 3600.0;
         a.dt_us = double(h->dt);
-        a.params = h->d_params.p;
-        a.set_ix = h->d_set_ix.p;
-        a.cellc = h->d_cellc.p;
-        a.state = h->d_state.p;
-        a.forcing = h->forcing_src ? h->forcing_src->d_forcing.p : h->d_forcing.p;
-        a.fcol = h->forcing_src ? h->d_fcol.p : nullptr;
-        a.f_cols = int(h->forcing_src ? h->forcing_src->n : h->n);
-        a.resp = h->d_resp.p;
-        a.state_series = h->collect_state ? h->d_state_series.p : nullptr;
-        a.active = h->active.empty() ? nullptr : h->d_active.p;
-        a.err = h->d_err.p;
-        a.uniform_params = h->n_sets == 1 ? 1 : 0;
-        a.nb_max = HBV_MAX_BINS;
-        if (h->pthsk()) {
-            a.nb_max = 0;
-            for (size_t k = 0; k < h->n_sets; ++k) a.nb_max = std::max(a.nb_max, int(h->params[k * PTHSK_NP + PH_NB]));
-        }
-        hip_check(hipEventRecord(h->ev0, h->stream), "hipEventRecord");
+        a.nb_max = nb_max;
         if (h->pthpsk())
             hip_check(launch_pthpsk_run(a, h->stream), "pthpsk_run_kernel launch");
         else if (h->pthsk())
             hip_check(launch_pthsk_run(a, h->stream), "pthsk_run_kernel launch");
         else
             hip_check(launch_ptssk_run(a, h->stream), "ptssk_run_kernel launch");
-        hip_check(hipEventRecord(h->ev1, h->stream), "hipEventRecord");
-        return;
-    }
-    if (h->hbv()) {
+    } else if (h->hbv()) {
         hbv_kargs a;
-        a.n_cells = int(h->n);
-        a.step0 = int(b);
-        a.n_steps = int(e - b);
-        a.win0 = int(h->w0);
-        a.win_len = int(h->TW);
-        a.collect = h->collect;
-        const double dt_s = double(h->dt) / 1e6;  // to_seconds(t1 - t0)
+        fill_common(a, h, b, e);
         a.step_in_days = dt_s / 86400.0;
         a.dt_hours = dt_s / 3600.0;
-        a.params = h->d_params.p;
-        a.set_ix = h->d_set_ix.p;
-        a.cellc = h->d_cellc.p;
-        a.state = h->d_state.p;
-        a.forcing = h->forcing_src ? h->forcing_src->d_forcing.p : h->d_forcing.p;
-        a.fcol = h->forcing_src ? h->d_fcol.p : nullptr;
-        a.f_cols = int(h->forcing_src ? h->forcing_src->n : h->n);
-        a.resp = h->d_resp.p;
-        a.state_series = h->collect_state ? h->d_state_series.p : nullptr;
-        a.active = h->active.empty() ? nullptr : h->d_active.p;
-        a.err = h->d_err.p;
-        a.uniform_params = h->n_sets == 1 ? 1 : 0;
-        a.nb_max = 0;
-        for (size_t k = 0; k < h->n_sets; ++k) {
-            const int nb = int(h->params[k * HBV_NP + HK_NB]);
-            if (nb > a.nb_max) a.nb_max = nb;
-        }
-        hip_check(hipEventRecord(h->ev0, h->stream), "hipEventRecord");
+        a.nb_max = nb_max;
         hip_check(launch_hbv_run(a, h->stream), "hbv_run_kernel launch");
-        hip_check(hipEventRecord(h->ev1, h->stream), "hipEventRecord");
-        return;
+    } else {
+        ptgsk_kargs a;
+        fill_common(a, h, b, e);
+        a.dt_s = dt_s;
+        a.dt_us = double(h->dt);
+        a.t1_hours = a.dt_s / 3600.0;  // to_seconds(T1-T0)/to_seconds(deltahours(1))
+        a.doy = h->d_doy.p;
+        a.t_rel_year_us = h->d_trel.p;
+        a.instance = h->knob_instance;
+        a.read_delay = h->knob_read_delay;
+        hip_check(launch_ptgsk_run(a, h->stream), "ptgsk_run_kernel launch");
     }
-    ptgsk_kargs a;
-    a.n_cells = int(h->n);
-    a.step0 = int(b);
-    a.n_steps = int(e - b);
-    a.win0 = int(h->w0);
-    a.win_len = int(h->TW);
-    a.collect = h->collect;
-    a.uniform_params = h->n_sets == 1 ? 1 : 0;
-    a.dt_s = double(h->dt) / 1e6;
-    a.dt_us = double(h->dt);
-    a.t1_hours = a.dt_s / 3600.0;  // to_seconds(T1-T0)/to_seconds(deltahours(1))
-    a.doy = h->d_doy.p;
-    a.t_rel_year_us = h->d_trel.p;
-    a.params = h->d_params.p;
-    a.set_ix = h->d_set_ix.p;
-    a.cellc = h->d_cellc.p;
-    a.state = h->d_state.p;
-    a.forcing = h->forcing_src ? h->forcing_src->d_forcing.p : h->d_forcing.p;
-    a.fcol = h->forcing_src ? h->d_fcol.p : nullptr;
-    a.f_cols = int(h->forcing_src ? h->forcing_src->n : h->n);
-    a.resp = h->d_resp.p;
-    a.state_series = h->collect_state ? h->d_state_series.p : nullptr;
-    a.active = h->active.empty() ? nullptr : h->d_active.p;
-    a.err = h->d_err.p;
-    a.instance = h->knob_instance;
-    a.read_delay = h->knob_read_delay;
-    hip_check(hipEventRecord(h->ev0, h->stream), "hipEventRecord");
-    hip_check(launch_ptgsk_run(a, h->stream), "ptgsk_run_kernel launch");
     hip_check(hipEventRecord(h->ev1, h->stream), "hipEventRecord");
 }
 
 static void finish_run(shyft_hip_region* h) {
-    hip_check(hipStreamSynchronize(h->stream), h->hbv() ? "hbv_run_kernel"
-                                               : h->ptssk() ? "ptssk_run_kernel"
-                                               : h->pthsk() ? "pthsk_run_kernel"
-                                               : h->pthpsk() ? "pthpsk_run_kernel" : "ptgsk_run_kernel");
+    hip_check(hipStreamSynchronize(h->stream), h->sd->run_kernel);
     float ms = 0.f;
     hip_check(hipEventElapsedTime(&ms, h->ev0, h->ev1), "hipEventElapsedTime");
     h->last_ms = ms;
@@ -1470,7 +1380,7 @@ int shyft_hip_catchment_area_sums(const shyft_hip_region* hc, int series, size_t
         const double* src = series_rows(h, series, step0, n, "catchment_area_sums");
         update_derived(h);  // per-cell constants (cell area) are current
         const size_t C = h->cix_to_cid.size();
-        const double* w = h->d_cellc.p + size_t(h->hbv() ? HC_AREA : PC_AREA) * h->n;
+        const double* w = h->d_cellc.p + size_t(h->sd->c_area) * h->n;
         double* out = dst;
         if (!dst_on_device) {
             h->d_tmp.alloc(std::max(h->d_tmp.n, C * n));
@@ -1631,6 +1541,7 @@ int shyft_hip_region_clone(const shyft_hip_region* src, shyft_hip_region** out) 
         try {
             std::unique_ptr<shyft_hip_region> c(new shyft_hip_region());
             c->stack = src->stack;
+            c->sd = src->sd;
             c->n = src->n;
             c->device = src->device;
             c->sh = shards::clone(src->sh);
@@ -2029,7 +1940,7 @@ int shyft_hip_ensemble_sums(const shyft_hip_region* hc, int series, int area_wei
         const size_t L = x->n, G = x->ens_groups;
         const double* src = x->d_resp.p + (size_t(series) * x->TW + (step0 - x->w0)) * L;
         const double* w = nullptr;
-        if (area_weighted) w = x->d_cellc.p + size_t(x->hbv() ? HC_AREA : PC_AREA) * L;
+        if (area_weighted) w = x->d_cellc.p + size_t(x->sd->c_area) * L;
         double* out = dst;
         if (!dst_on_device) {
             x->d_tmp.alloc(std::max(x->d_tmp.n, G * n));

@@ -3,7 +3,7 @@
 usage (GPU box): python tools/ptssk_phases.py lib.so [cells]
 Runs the bench region from Jan 1 through 12 chunks of 730 steps and prints, per chunk, the kernel ms and the share of
 wavefront time in: front (forcing + ss_front), queue (job queue + first barrier), jobs (sca_rel_red evaluation; ~0 on
-wavefronts without jobs), wait (second barrier), back (ss_back, glacier), pt+kirchner (PT, AE, kirchner, stores); for
+wavefronts without jobs), wait (second barrier), back (ss_back), pt+kirchner (glacier, PT, AE, kirchner, stores); for
 the solving wavefronts the cycles per job phase and the job lanes per solving wavefront-step; and inside the jobs the
 share of each part (lgammas, opening evaluations, Brent + walk, bisection, final cdfs; s_memtime marks of the wavefronts
 running jobs, device/ptssk_dev.h SS_JOB_MARK)."""
