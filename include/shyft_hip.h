@@ -514,6 +514,34 @@ int shyft_hip_ts_min_max_fill_host(int device, size_t S, const int64_t* row, con
 double shyft_hip_tsprep_last_ms(int device);
 uint64_t shyft_hip_tsprep_calls(int device);
 
+/* Time-series arithmetic: E expressions over S terminal point series, every point of every expression in one launch
+ * of kernels/ts_expr.hip on a device (device < 0 = current). An expression is the reference's lazy apoint_ts tree of
+ * ts op ts, ts op scalar, scalar op ts (ADD SUB MUL DIV MAX MIN POW) and abs (core/time_series_dd.h:825-872, 1705-1890;
+ * core/time_series_dd.cpp:70-129, 197-224, 835-920), planned by host/ts_expr.hpp make_plan into a postfix program of
+ * int32 words; that header states the words, the two evaluation modes and the axis rules. The terminals are in the CSR
+ * form of shyft_hip_resample. Expression e runs prog[prog_row[e] .. prog_row[e+1]) at each of its output points
+ * orow[e] .. orow[e+1), whose times (the root axis, int64 microseconds) are ot; consts [n_const] and periods
+ * [n_period][2] = start, end are the tables the programs index. out [orow[E]] receives what the reference's values()
+ * gives for the expression, with detmath::pow for std::pow.
+ * Refused before anything is launched: malformed series (the texts of shyft_hip_resample, prefix "ts_expr"), rows that
+ * do not start at 0 or decrease, unknown words, operation, terminal, constant or period indexes out of range, a stack
+ * that underflows or does not end at depth 1, a LOAD_RAW of a terminal whose size is not the expression's, and, by the
+ * device entry only, a stack deeper than 8 values or a program longer than 64 words; _host evaluates those.
+ * E == 0 or orow[E] == 0 returns 0 and launches nothing. _host runs the interpreter of host/ts_expr.hpp on one thread
+ * and ignores device; the device result is bit-identical to it, NaN matching NaN. */
+int shyft_hip_ts_expr(int device, size_t S, const int64_t* row, const int64_t* t, const double* v, const int64_t* t_end,
+                      const int32_t* fx, size_t E, const int64_t* prog_row, const int32_t* prog, size_t n_const,
+                      const double* consts, size_t n_period, const int64_t* periods, const int64_t* orow,
+                      const int64_t* ot, double* out);
+int shyft_hip_ts_expr_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                           const int64_t* t_end, const int32_t* fx, size_t E, const int64_t* prog_row,
+                           const int32_t* prog, size_t n_const, const double* consts, size_t n_period,
+                           const int64_t* periods, const int64_t* orow, const int64_t* ot, double* out);
+/* HIP-event milliseconds of the kernel of the last shyft_hip_ts_expr call on this device, copies excluded, and the
+ * number of such calls that launched so far. (No reference counterpart: measurement and test aid.) */
+double shyft_hip_ts_expr_last_ms(int device);
+uint64_t shyft_hip_ts_expr_calls(int device);
+
 /* Forecast skill by lead time: the Nash-Sutcliffe score of P problems in one launch of kernels/forecast.hip on a device
  * (device < 0 = current). A problem is ats_vector::nash_sutcliffe(obs, t0_offset, dt, n)
  * (core/time_series_dd.cpp:1137-1145 -> core/time_series_merge.h:123-144): for each forecast in order the n slice

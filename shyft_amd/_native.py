@@ -89,6 +89,12 @@ SIGNATURES = {
     "shyft_hip_ts_min_max_fill_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 9),
     "shyft_hip_tsprep_last_ms": (C.c_double, [C.c_int]),
     "shyft_hip_tsprep_calls": (C.c_uint64, [C.c_int]),
+    "shyft_hip_ts_expr": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 2
+                          + [C.c_size_t, C.c_void_p] * 2 + [C.c_void_p] * 3),
+    "shyft_hip_ts_expr_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 2
+                               + [C.c_size_t, C.c_void_p] * 2 + [C.c_void_p] * 3),
+    "shyft_hip_ts_expr_last_ms": (C.c_double, [C.c_int]),
+    "shyft_hip_ts_expr_calls": (C.c_uint64, [C.c_int]),
     "shyft_hip_forecast_skill": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 9),
     "shyft_hip_forecast_skill_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t]
                                       + [C.c_void_p] * 9),

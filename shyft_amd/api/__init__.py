@@ -26,6 +26,8 @@ from ._api import (  # noqa: F401  (re-exported names)
 )
 from . import _api
 from . import _tsprep
+from . import _ts_expr
+from ._ts_expr import time_shift  # noqa: F401  (re-exported name)
 from ._tsprep import (  # noqa: F401  (re-exported names)
     RatingCurveSegment, RatingCurveFunction, RatingCurveParameters, IcePackingParameters,
     IcePackingRecessionParameters, ice_packing_temperature_policy, max_utctime,
@@ -139,11 +141,26 @@ class TimeSeries:
         self._ts = _api._PointTs(ta, [float(v) for v in np.asarray(values, dtype=np.float64)], point_fx)
         self._ta = ta
 
+    # An arithmetic result holds an expression tree (_expr, with its point type _fx) and no series (_impl) until it
+    # is read: _ts evaluates the tree on the host on first read and keeps the result. A concrete series has no tree.
+    _impl = _expr = _fx = None
+
+    @property
+    def _ts(self):
+        if self._impl is None:
+            _ts_expr.evaluate([self], host=True)
+        return self._impl
+
+    @_ts.setter
+    def _ts(self, impl):
+        self._impl, self._expr = impl, None
+
     def value(self, i):
         return self._ts.value(i)
 
     def set(self, i, v):
         self._ts.set(i, v)
+        self._expr = None  # from here on a concrete series: a later expression sees the new value
 
     def size(self):
         return self._ts.size()
@@ -158,6 +175,8 @@ class TimeSeries:
         return self._ts.time(i)
 
     def point_interpretation(self):
+        if self._impl is None:  # an expression answers from its tree, without evaluating
+            return self._fx
         return self._ts.point_interpretation()
 
     def total_period(self):
@@ -211,6 +230,57 @@ class TimeSeries:
         valid neighbours, NaN when those are more than dt_max seconds apart (qac_ts, time_series_dd.cpp:1335-1376);
         the source's point type"""
         return _tsprep.min_max_check_linear_fill([self], v_min, v_max, dt_max, True)[0]
+
+    # arithmetic (time_series_dd.cpp:94-122, 922-928): every result is a lazy expression, the other operand a
+    # TimeSeries or a number. Nothing is computed until the result is read or evaluated.
+    def __add__(self, o):
+        return _ts_expr.binary(_ts_expr.ADD, self, o)
+
+    def __radd__(self, o):
+        return _ts_expr.binary(_ts_expr.ADD, o, self)
+
+    def __sub__(self, o):
+        return _ts_expr.binary(_ts_expr.SUB, self, o)
+
+    def __rsub__(self, o):
+        return _ts_expr.binary(_ts_expr.SUB, o, self)
+
+    def __mul__(self, o):
+        return _ts_expr.binary(_ts_expr.MUL, self, o)
+
+    def __rmul__(self, o):
+        return _ts_expr.binary(_ts_expr.MUL, o, self)
+
+    def __truediv__(self, o):
+        return _ts_expr.binary(_ts_expr.DIV, self, o)
+
+    def __rtruediv__(self, o):
+        return _ts_expr.binary(_ts_expr.DIV, o, self)
+
+    def __neg__(self):
+        return _ts_expr.binary(_ts_expr.MUL, -1.0, self)  # time_series_dd.cpp:101
+
+    def min(self, x):
+        return _ts_expr.function(_ts_expr.MIN, self, x)
+
+    def max(self, x):
+        return _ts_expr.function(_ts_expr.MAX, self, x)
+
+    def pow(self, x):
+        return _ts_expr.function(_ts_expr.POW, self, x)
+
+    def abs(self):
+        return _ts_expr.absolute(self)
+
+    def time_shift(self, dt):
+        """this series dt seconds later (time_shift_ts, time_series_dd.h:707-751)"""
+        return _ts_expr.shifted(self, dt)
+
+    def evaluate(self, *, host=False):
+        """the concrete series of this expression: one device call, or with host=True the host restatement,
+        bit-identical. The result is kept, so reading this series afterwards computes nothing."""
+        import copy
+        return TimeSeries(_impl=copy.deepcopy(_ts_expr.evaluate([self], host)[0]))
 
 
 # ---- average / integral / accumulate of a set of series in one call (region.resample) -------------------------------
@@ -396,6 +466,56 @@ class TsVector(_Vector):
             raise RuntimeError("nash_sutcliffe needs equal sized ts accessors with elements >1")
         return float(forecast_skill(TsVectorSet([self]), TsVector([observation_ts]), [lead_time], delta_t, n,
                                     host=host)[0, 0])
+
+    # arithmetic, element by element with a number, a TimeSeries or a TsVector of the same length (ats_vector,
+    # time_series_dd.cpp:1007-1118); the elements of the result are lazy expressions
+    def __add__(self, o):
+        return _ts_expr.vector_binary(_ts_expr.ADD, self, o)
+
+    def __radd__(self, o):
+        return _ts_expr.vector_binary(_ts_expr.ADD, o, self)
+
+    def __sub__(self, o):
+        return _ts_expr.vector_binary(_ts_expr.SUB, self, o)
+
+    def __rsub__(self, o):
+        return _ts_expr.vector_binary(_ts_expr.SUB, o, self)
+
+    def __mul__(self, o):
+        return _ts_expr.vector_binary(_ts_expr.MUL, self, o)
+
+    def __rmul__(self, o):
+        return _ts_expr.vector_binary(_ts_expr.MUL, o, self)
+
+    def __truediv__(self, o):
+        return _ts_expr.vector_binary(_ts_expr.DIV, self, o)
+
+    def __rtruediv__(self, o):
+        return _ts_expr.vector_binary(_ts_expr.DIV, o, self)
+
+    def __neg__(self):
+        return TsVector(-ts for ts in self)
+
+    def min(self, x):
+        return _ts_expr.function(_ts_expr.MIN, self, x)
+
+    def max(self, x):
+        return _ts_expr.function(_ts_expr.MAX, self, x)
+
+    def pow(self, x):
+        return _ts_expr.function(_ts_expr.POW, self, x)
+
+    def abs(self):
+        return TsVector(ts.abs() for ts in self)
+
+    def time_shift(self, dt):
+        return _ts_expr.time_shift(self, dt)
+
+    def evaluate(self, *, host=False):
+        """the concrete series of every element, all expressions in one device call (region.ts_expr_csr), or with
+        host=True on the host, bit-identical"""
+        import copy
+        return TsVector(TimeSeries(_impl=copy.deepcopy(impl)) for impl in _ts_expr.evaluate(list(self), host))
 
     def forecast_merge(self, lead_time, fc_interval):
         """one series from the slice [time(0) + lead_time, + fc_interval) of every forecast, a missing forecast filled
@@ -1377,3 +1497,12 @@ def _make_models(prefix, base_cls, native_model, native_optimizer, docs):
     for m in (model, opt_model):
         m.optimizer_t, m.parameter_t, m.state_t = optimizer, parameter_t, base_cls._state_t
     return model, opt_model, create_opt_model_clone, create_full_model_clone, optimizer
+
+
+def __getattr__(name):
+    """api.min, api.max and api.pow (time_series_dd.cpp:112-122, 1090-1118). They are served on attribute access
+    (`api.max(ts, 300.0)`, `from shyft_amd.api import max`) and are not globals of this module, whose own code keeps
+    the builtins of those names."""
+    if name in ("min", "max", "pow"):
+        return getattr(_ts_expr, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -21,6 +21,7 @@
 #include "kalman.hpp"
 #include "qm.hpp"
 #include "region_model.hpp"
+#include "ts_expr.hpp"
 
 namespace py = pybind11;
 using namespace shyft_hip::host;
@@ -53,6 +54,73 @@ py::tuple series_csr(const py::list& series) {
         std::copy(src[s]->v.begin(), src[s]->v.end(), v.mutable_data() + r[s]);
     }
     return py::make_tuple(row, t, v, t_end, fx);
+}
+
+// An expression tree from Python into expr::tree. A terminal is a _PointTs; any other node a tuple (kind, op, a, b)
+// with kind and op of host/ts_expr.hpp: a and b trees for TS_TS, a tree and a float for TS_S and S_TS (the series
+// first in both), a tree and None for ABS_TS. A series that occurs more than once is one terminal of the batch.
+int32_t add_expr_node(const py::handle& h, expr::tree& tr, py::list& series, std::map<const point_ts*, int32_t>& index) {
+    expr::node x;
+    if (py::isinstance<point_ts>(h)) {
+        const point_ts* p = &h.cast<const point_ts&>();
+        auto it = index.find(p);
+        if (it == index.end()) {
+            it = index.emplace(p, int32_t(series.size())).first;
+            series.append(h);
+        }
+        x.kind = expr::TERMINAL;
+        x.a = it->second;
+    } else {
+        const py::tuple tu = h.cast<py::tuple>();
+        if (tu.size() != 4) throw std::runtime_error("ts_expr: a node is a series or a tuple (kind, op, a, b)");
+        x.kind = tu[0].cast<int32_t>();
+        x.op = tu[1].cast<int32_t>();
+        x.a = add_expr_node(tu[2], tr, series, index);
+        if (x.kind == expr::TS_TS) x.b = add_expr_node(tu[3], tr, series, index);
+        else if (x.kind == expr::TS_S || x.kind == expr::S_TS) x.s = tu[3].cast<double>();
+    }
+    tr.nodes.push_back(x);
+    return int32_t(tr.nodes.size() - 1);
+}
+
+template <class T>
+py::array_t<T> as_array(const std::vector<T>& v) {
+    return py::array_t<T>(py::ssize_t(v.size()), v.data());
+}
+
+// The plans of a list of trees: (terminals, prog_row, prog, consts, periods, orow, ot, fx, t_end, depth). terminals
+// is the list of distinct _PointTs in terminal order (for _series_csr); fx, t_end and depth are per expression: the
+// root's point type, the end of the root axis, and the deepest evaluation stack.
+py::tuple ts_expr_plan(const py::list& trees) {
+    py::list series;
+    std::map<const point_ts*, int32_t> index;
+    std::vector<expr::tree> parsed;
+    for (auto h : trees) {
+        parsed.emplace_back();
+        add_expr_node(h, parsed.back(), series, index);
+    }
+    std::vector<expr::terminal> terminals;
+    for (auto h : series) {
+        const point_ts& s = h.cast<const point_ts&>();
+        terminals.push_back({expr::axis{s.t, s.t_end}, s.fx});
+    }
+    expr::tables tb;
+    std::vector<int64_t> prog_row{0}, orow{0}, ot, t_end;
+    std::vector<int32_t> prog, fx, depth;
+    for (const auto& tr : parsed) {
+        const expr::plan p = expr::make_plan(tr, terminals, tb);
+        prog.insert(prog.end(), p.prog.begin(), p.prog.end());
+        prog_row.push_back(int64_t(prog.size()));
+        ot.insert(ot.end(), p.ta.t.begin(), p.ta.t.end());
+        orow.push_back(int64_t(ot.size()));
+        fx.push_back(int32_t(p.fx));
+        t_end.push_back(p.ta.t_end);
+        depth.push_back(p.depth);
+    }
+    py::array_t<int64_t> periods({py::ssize_t(tb.periods.size() / 2), py::ssize_t(2)});
+    std::copy(tb.periods.begin(), tb.periods.end(), periods.mutable_data());
+    return py::make_tuple(series, as_array(prog_row), as_array(prog), as_array(tb.consts), periods, as_array(orow),
+                          as_array(ot), as_array(fx), as_array(t_end), as_array(depth));
 }
 
 template <class Stack>
@@ -295,6 +363,20 @@ PYBIND11_MODULE(_api, m) {
             return r;
         })
         .def("_total_period_us", [](const point_ts& s) { auto p = s.total_period(); return std::make_pair(p.start, p.end); })
+        // the series with dt [s] added to every time and to t_end (a terminal under time_shift, host/ts_expr.hpp)
+        .def("_shifted", [](const point_ts& s, double dt) {
+            point_ts r(s);
+            const utctime d = to_us(dt);
+            for (auto& x : r.t) x += d;
+            r.t_end += d;
+            return r;
+        })
+        // a series from times in microseconds (the root axis of an expression); no points is the empty series
+        .def_static("_from_us", [](const py::array_t<int64_t, py::array::c_style | py::array::forcecast>& t, utctime t_end,
+                                   const py::array_t<double, py::array::c_style | py::array::forcecast>& v, ts_point_fx fx) {
+            return point_ts(std::vector<utctime>(t.data(), t.data() + t.size()), t_end,
+                            std::vector<double>(v.data(), v.data() + v.size()), fx);
+        })
         .def("average", [](const point_ts& s, const fixed_dt& ta) {
             auto v = average_values(s, ta);
             return py::array_t<double>(v.size(), v.data());
@@ -634,6 +716,7 @@ PYBIND11_MODULE(_api, m) {
     // The host work of region.forecast_skill_csr callers: the CSR arrays alone, and seconds as ticks.
     m.def("_series_csr", &series_csr);
     m.def("_to_us", &to_us);
+    m.def("_ts_expr_plan", &ts_expr_plan);
     // TsVector.forecast_merge (host/forecast.hpp; core/time_series_merge.h:47-99)
     m.def("_forecast_merge", [](const py::list& series, double lead_time, double fc_interval) {
         std::vector<const point_ts*> tsv;

@@ -762,3 +762,42 @@ def forecast_skill_last_ms(device: int = -1) -> float:
 def forecast_skill_calls(device: int = -1) -> int:
     """The number of forecast_skill_csr device calls that launched on the device so far."""
     return int(lib().shyft_hip_forecast_skill_calls(device))
+
+
+# ---- time-series arithmetic (kernels/ts_expr.hip) ---------------------------------------------------------------------
+def ts_expr_csr(row, t, v, t_end, fx, prog_row, prog, consts, periods, orow, ot, device: int = -1,
+                host: bool = False) -> np.ndarray:
+    """E expressions over S terminal series, every point of every expression in one device call (shyft_hip_ts_expr;
+    the reference's lazy apoint_ts arithmetic, core/time_series_dd.cpp:70-129, 197-224, 835-920). The terminals are in
+    the CSR form of resample_csr. Expression e runs the postfix program prog[prog_row[e]:prog_row[e+1]] (int32 words,
+    csrc/host/ts_expr.hpp; api._api._ts_expr_plan makes them from trees) at its output points orow[e]:orow[e+1], whose
+    times (int64 microseconds) are ot; consts and periods [n][2] are the tables the programs index. Returns
+    [orow[E]]. The device entry refuses a stack deeper than 8 values or a program longer than 64 words; host=True runs
+    the host interpreter, which has no such limit and which the device is bit-identical to."""
+    S, row, t, v, t_end, fx = _csr_series("ts_expr", row, t, v, t_end, fx)
+    prog_row = np.ascontiguousarray(prog_row, dtype=np.int64).reshape(-1)
+    prog = np.ascontiguousarray(prog, dtype=np.int32).reshape(-1)
+    consts = np.ascontiguousarray(consts, dtype=np.float64).reshape(-1)
+    periods = np.ascontiguousarray(periods, dtype=np.int64).reshape(-1, 2)
+    orow = np.ascontiguousarray(orow, dtype=np.int64).reshape(-1)
+    ot = np.ascontiguousarray(ot, dtype=np.int64).reshape(-1)
+    E = prog_row.shape[0] - 1
+    if E < 0 or orow.shape[0] != E + 1:
+        raise ValueError("ts_expr: prog_row and orow must have one entry more than there are expressions")
+    if E and (prog_row[-1] != prog.shape[0] or orow[-1] != ot.shape[0]):
+        raise ValueError("ts_expr: prog_row must end at the number of words and orow at the number of output points")
+    out = np.empty(ot.shape[0] if E else 0, dtype=np.float64)
+    fn = lib().shyft_hip_ts_expr_host if host else lib().shyft_hip_ts_expr
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), E, _ptr(prog_row), _ptr(prog),
+             consts.shape[0], _ptr(consts), periods.shape[0], _ptr(periods), _ptr(orow), _ptr(ot), _ptr(out)), None)
+    return out
+
+
+def ts_expr_last_ms(device: int = -1) -> float:
+    """HIP-event milliseconds of the kernel of the last ts_expr_csr device call on the device, copies excluded."""
+    return float(lib().shyft_hip_ts_expr_last_ms(device))
+
+
+def ts_expr_calls(device: int = -1) -> int:
+    """The number of ts_expr_csr device calls that launched on the device so far."""
+    return int(lib().shyft_hip_ts_expr_calls(device))
