@@ -514,6 +514,71 @@ int shyft_hip_ts_min_max_fill_host(int device, size_t S, const int64_t* row, con
 double shyft_hip_tsprep_last_ms(int device);
 uint64_t shyft_hip_tsprep_calls(int device);
 
+/* The point-wise filter series of S point series in one device call each (kernels/tsfilter.hip; device < 0 = current).
+ * Host pointers, stateless. The series are in the CSR form of shyft_hip_resample and are checked in the same way and
+ * with the same texts (prefix "ts_filter") before anything is launched. out holds one double per input point in the
+ * same CSR order. A refused batch launches nothing; S == 0 or zero points returns 0 and launches nothing. Every
+ * operation is evaluated as written (int64 ticks, to_seconds as a division, no FMA), so each entry is bit-identical to
+ * its _host twin, which runs host/ts_filter.hpp on one thread and does not use `device`.
+ *
+ * shyft_hip_ts_convolve_w replaces convolve_w_ts::value(i) (core/time_series.h:966-975; apoint_ts::convolve_w,
+ * core/time_series_dd.h:919-950): v = 0.0, then for j = 0 .. K-1 in that order v += w[j] * x[i-j], and where j > i the
+ * policy's stand-in: 0 USE_FIRST w[j] * x[0], 1 USE_ZERO 0.0, 2 USE_NAN NaN. The weight profiles are a CSR, w_row [W+1]
+ * offsets into w; w_of [S] names the profile of a series, policy [S] its policy. A profile without weights gives 0.0.
+ * Refused: a w_row that does not start at 0 or decreases, w_of outside [0, W), a policy outside 0..2 and, by the
+ * device entry only, a used profile of more than 65,536 weights. */
+int shyft_hip_ts_convolve_w(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                            const int64_t* t_end, const int32_t* fx, size_t W, const int64_t* w_row, const double* w,
+                            const int64_t* w_of, const int32_t* policy, double* out);
+int shyft_hip_ts_convolve_w_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                                 const int64_t* t_end, const int32_t* fx, size_t W, const int64_t* w_row,
+                                 const double* w, const int64_t* w_of, const int32_t* policy, double* out);
+/* shyft_hip_ts_derivative replaces derivative_ts::values() (core/time_series_dd.cpp:450-463) with derivative_fx
+ * (:311-448). A POINT_INSTANT_VALUE series gives the slope to the next point and NaN at its last point; a
+ * POINT_AVERAGE_VALUE series the method's difference, method [S]: 0 default (= center), 1 forward, 2 backward,
+ * 3 center, with the reference's rules for non-finite neighbours. fixed_dt [S] (ticks) > 0 takes the reference's
+ * fixed-step branch and must be the spacing of every point of the series and of t_end; 0 takes the variable branch.
+ * Refused: a method outside 0..3, fixed_dt < 0, a fixed_dt > 0 that is not the series' spacing. */
+int shyft_hip_ts_derivative(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                            const int64_t* t_end, const int32_t* fx, const int64_t* fixed_dt, const int32_t* method,
+                            double* out);
+int shyft_hip_ts_derivative_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                                 const int64_t* t_end, const int32_t* fx, const int64_t* fixed_dt,
+                                 const int32_t* method, double* out);
+/* shyft_hip_ts_inside replaces inside_ts::values() = inside_parameter::inside_value per point
+ * (core/time_series_dd.h:1546-1554; core/time_series_dd.cpp:1409-1426): nan_x for a non-finite value, x_outside below
+ * a finite min_x or at or above a finite max_x, x_inside otherwise. Each parameter is [S]. */
+int shyft_hip_ts_inside(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                        const int64_t* t_end, const int32_t* fx, const double* min_x, const double* max_x,
+                        const double* nan_x, const double* x_inside, const double* x_outside, double* out);
+int shyft_hip_ts_inside_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                             const int64_t* t_end, const int32_t* fx, const double* min_x, const double* max_x,
+                             const double* nan_x, const double* x_inside, const double* x_outside, double* out);
+/* shyft_hip_ts_decode replaces decode_ts::values() = bit_decoder::decode per point (core/time_series_dd.h:1650-1655;
+ * core/time_series_dd.cpp:1428-1445): NaN for a non-finite or negative value or one above 2^52, else the n_bits [S]
+ * bits from start_bit [S] of the value as an unsigned integer. Refused with the texts of apoint_ts::decode
+ * (core/time_series_dd.cpp:943-946): "start_bit must be in range [0..51], was N" and "n_bits must be > 0 and
+ * start_bit+n_bits <= 51: n_bits =N, start_bit=M". */
+int shyft_hip_ts_decode(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                        const int64_t* t_end, const int32_t* fx, const int32_t* start_bit, const int32_t* n_bits,
+                        double* out);
+int shyft_hip_ts_decode_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                             const int64_t* t_end, const int32_t* fx, const int32_t* start_bit, const int32_t* n_bits,
+                             double* out);
+/* HIP-event milliseconds of the kernel of the last of these four device calls on this device, copies excluded, and the
+ * number of such calls that launched so far. (No reference counterpart: measurement and test aid.) */
+double shyft_hip_tsfilter_last_ms(int device);
+uint64_t shyft_hip_tsfilter_calls(int device);
+/* The launch shape of shyft_hip_ts_convolve_w: DIRECT, one lane per point with taps and values from global memory;
+ * TILED, a workgroup per 256 consecutive points of one series, the values staged through LDS in chunks of 256 taps.
+ * AUTO takes TILED from 2 weights on when the tiles are at least a quarter full on average. set_path is process-wide;
+ * last_path reports what the last convolve_w on the device ran. (No reference counterpart: test and measurement aid.) */
+#define SHYFT_HIP_TSFILTER_PATH_AUTO 0
+#define SHYFT_HIP_TSFILTER_PATH_DIRECT 1
+#define SHYFT_HIP_TSFILTER_PATH_TILED 2
+int shyft_hip_tsfilter_set_path(int path);
+int shyft_hip_tsfilter_last_path(int device);
+
 /* Time-series arithmetic: E expressions over S terminal point series, every point of every expression in one launch
  * of kernels/ts_expr.hip on a device (device < 0 = current). An expression is the reference's lazy apoint_ts tree of
  * ts op ts, ts op scalar, scalar op ts (ADD SUB MUL DIV MAX MIN POW) and abs (core/time_series_dd.h:825-872, 1705-1890;

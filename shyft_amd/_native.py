@@ -89,6 +89,19 @@ SIGNATURES = {
     "shyft_hip_ts_min_max_fill_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 9),
     "shyft_hip_tsprep_last_ms": (C.c_double, [C.c_int]),
     "shyft_hip_tsprep_calls": (C.c_uint64, [C.c_int]),
+    "shyft_hip_ts_convolve_w": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 5),
+    "shyft_hip_ts_convolve_w_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t]
+                                     + [C.c_void_p] * 5),
+    "shyft_hip_ts_derivative": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 8),
+    "shyft_hip_ts_derivative_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 8),
+    "shyft_hip_ts_inside": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 11),
+    "shyft_hip_ts_inside_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 11),
+    "shyft_hip_ts_decode": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 8),
+    "shyft_hip_ts_decode_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 8),
+    "shyft_hip_tsfilter_last_ms": (C.c_double, [C.c_int]),
+    "shyft_hip_tsfilter_calls": (C.c_uint64, [C.c_int]),
+    "shyft_hip_tsfilter_set_path": (C.c_int, [C.c_int]),
+    "shyft_hip_tsfilter_last_path": (C.c_int, [C.c_int]),
     "shyft_hip_ts_expr": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 2
                           + [C.c_size_t, C.c_void_p] * 2 + [C.c_void_p] * 3),
     "shyft_hip_ts_expr_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 2

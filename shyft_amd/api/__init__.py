@@ -33,6 +33,12 @@ from ._tsprep import (  # noqa: F401  (re-exported names)
     IcePackingRecessionParameters, ice_packing_temperature_policy, max_utctime,
 )
 
+from . import _tsfilter
+from ._tsfilter import convolve_policy, derivative_method  # noqa: F401  (re-exported names)
+
+USE_FIRST, USE_ZERO, USE_NAN = convolve_policy.USE_FIRST, convolve_policy.USE_ZERO, convolve_policy.USE_NAN
+DEFAULT, FORWARD, BACKWARD, CENTER = (derivative_method.DEFAULT, derivative_method.FORWARD, derivative_method.BACKWARD,
+                                      derivative_method.CENTER)
 DISALLOW_MISSING = ice_packing_temperature_policy.DISALLOW_MISSING
 ALLOW_INITIAL_MISSING = ice_packing_temperature_policy.ALLOW_INITIAL_MISSING
 ALLOW_ANY_MISSING = ice_packing_temperature_policy.ALLOW_ANY_MISSING
@@ -230,6 +236,29 @@ class TimeSeries:
         valid neighbours, NaN when those are more than dt_max seconds apart (qac_ts, time_series_dd.cpp:1335-1376);
         the source's point type"""
         return _tsprep.min_max_check_linear_fill([self], v_min, v_max, dt_max, True)[0]
+
+    # point-wise filters (api_time_series.cpp; time_series_dd.cpp:494-496, 930-948), one series on the host
+    def convolve_w(self, weights, policy):
+        """this series convolved with the weights: value(i) = sum_j weights[j] * value(i - j), the convolve_policy
+        standing in for the values before the first point (convolve_w_ts, time_series.h:905-980); the source's point
+        type"""
+        return _tsfilter.convolve_w([self], weights, policy, True)[0]
+
+    def derivative(self, method=_tsfilter.derivative_method.DEFAULT):
+        """the derivative of this series: the slope between points for a POINT_INSTANT_VALUE series, the
+        derivative_method's difference for a stair-case one (derivative_ts, time_series_dd.cpp:311-463);
+        POINT_AVERAGE_VALUE"""
+        return _tsfilter.derivative([self], method, True)[0]
+
+    def inside(self, min_v, max_v, nan_v=float("nan"), inside_v=1.0, outside_v=0.0):
+        """inside_v where min_v <= value < max_v (a NaN limit is no limit), outside_v where not, nan_v where the value
+        is not finite (inside_ts, time_series_dd.h:1538-1607); the source's point type"""
+        return _tsfilter.inside([self], min_v, max_v, nan_v, inside_v, outside_v, True)[0]
+
+    def decode(self, start_bit, n_bits):
+        """n_bits bits from start_bit of the values taken as unsigned integers; NaN for a value that is not finite,
+        negative or above 2^52 (decode_ts, time_series_dd.h:1609-1700); the source's point type"""
+        return _tsfilter.decode([self], start_bit, n_bits, True)[0]
 
     # arithmetic (time_series_dd.cpp:94-122, 922-928): every result is a lazy expression, the other operand a
     # TimeSeries or a number. Nothing is computed until the result is read or evaluated.
@@ -433,6 +462,22 @@ class TsVector(_Vector):
 
     def min_max_check_linear_fill(self, v_min, v_max, dt_max=_tsprep.max_utctime, *, host=False):
         return _tsprep.min_max_check_linear_fill(self, v_min, v_max, dt_max, host)
+
+    # point-wise filters: the TimeSeries methods of the same names for every series, each one device call
+    # (region.ts_*_csr), or with host=True on the host, bit-identical. derivative and inside are the reference's
+    # (api_time_series.cpp:248, :340); convolve_w and decode are this engine's batched forms. A parameter is one value
+    # for all series or a sequence of len(self); `weights` is one profile for all series or a sequence of profiles.
+    def convolve_w(self, weights, policy, *, host=False):
+        return _tsfilter.convolve_w(self, weights, policy, host)
+
+    def derivative(self, method=_tsfilter.derivative_method.DEFAULT, *, host=False):
+        return _tsfilter.derivative(self, method, host)
+
+    def inside(self, min_v, max_v, nan_v=float("nan"), inside_v=1.0, outside_v=0.0, *, host=False):
+        return _tsfilter.inside(self, min_v, max_v, nan_v, inside_v, outside_v, host)
+
+    def decode(self, start_bit, n_bits, *, host=False):
+        return _tsfilter.decode(self, start_bit, n_bits, host)
 
     # forecast skill by lead time and the forecast merge (time_series_dd.cpp:1120-1165, api_time_series.cpp:299-339)
     def average_slice(self, lead_time, delta_t, n, *, host=False):

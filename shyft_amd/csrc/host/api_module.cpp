@@ -348,6 +348,8 @@ PYBIND11_MODULE(_api, m) {
             return t;
         })
         .def_property_readonly("_t_end", [](const point_ts& s) { return to_s(s.t_end); })
+        // the step [us] of the TimeAxisFixedDeltaT the series was built on, 0 for any other series (derivative)
+        .def_property_readonly("_fixed_dt_us", [](const point_ts& s) { return s.fixed_step; })
         // the series on the same points with other values (the results of the observation-preparation calls)
         .def("_with_values", [](const point_ts& s, const std::vector<double>& v, ts_point_fx fx) {
             if (v.size() != s.size()) throw std::runtime_error("point_ts: values and time-axis differ in size");

@@ -71,14 +71,19 @@ struct point_ts {
     utctime t_end = 0;
     std::vector<double> v;
     ts_point_fx fx = POINT_AVERAGE_VALUE;
+    // the step of the fixed_dt axis the series was built on, 0 for any other series: derivative takes the reference's
+    // fixed-step branch for a series on a fixed axis (fixed_timestep, core/time_series_dd.cpp:274-290)
+    utctimespan fixed_step = 0;
 
     point_ts() = default;
-    point_ts(const fixed_dt& ta, double fill, ts_point_fx f = POINT_AVERAGE_VALUE) : v(ta.size(), fill), fx(f) {
+    point_ts(const fixed_dt& ta, double fill, ts_point_fx f = POINT_AVERAGE_VALUE)
+        : v(ta.size(), fill), fx(f), fixed_step(ta.dt > 0 ? ta.dt : 0) {
         t.resize(ta.size());
         for (size_t i = 0; i < ta.size(); ++i) t[i] = ta.time(i);
         t_end = ta.total_period().end;
     }
-    point_ts(const fixed_dt& ta, std::vector<double> values, ts_point_fx f) : v(std::move(values)), fx(f) {
+    point_ts(const fixed_dt& ta, std::vector<double> values, ts_point_fx f)
+        : v(std::move(values)), fx(f), fixed_step(ta.dt > 0 ? ta.dt : 0) {
         if (v.size() != ta.size()) throw std::runtime_error("point_ts: values and time-axis differ in size");
         t.resize(ta.size());
         for (size_t i = 0; i < ta.size(); ++i) t[i] = ta.time(i);

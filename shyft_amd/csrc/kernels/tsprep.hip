@@ -42,8 +42,8 @@
 // Index safety. The host checks before any launch that row[0] == 0 and row is non-decreasing, so row[S] = np points
 // were uploaded, that times increase strictly in a series and t_end lies after the last, that pack_of[s] < P and the
 // three CSR levels of the packs are non-decreasing and end at the uploaded sizes, and that qrow is a CSR of nq
-// queries. A lane's point k (or query j) is < np (< nq) by its grid-stride test; tp_series_of returns the s < S with
-// row[s] <= k < row[s+1], which exists because k < row[S]. RATING reads curve it in [c0, c1) after the `c0 == c1` test
+// queries. A lane's point k (or query j) is < np (< nq) by its grid-stride test; csr_series_of (device/csr_series.h)
+// returns the s < S with row[s] <= k < row[s+1], which exists because k < row[S]. RATING reads curve it in [c0, c1) after the `c0 == c1` test
 // and segment g in [g0, g1) after `g0 == g1`. ICE passes rs_area the n > 0 points of one series (device/ts_area.h
 // states its own reads). The scan kernels read key sources at positions < np only and write L at positions < np and
 // agg at block indexes < nb; LDS is indexed by the wavefront number < 4. The finish kernels read L[k - 1] only with
@@ -60,6 +60,7 @@
 #include <vector>
 
 #include "../../../detmath/detmath.h"
+#include "../device/csr_series.h"
 #include "../device/ts_area.h"
 #include "../host/ts_prep.hpp"
 #include "../include_internal/device_call.h"
@@ -73,17 +74,6 @@ constexpr int TP_BLOCK = 256;                      // 4 wavefronts
 constexpr int TP_ITEMS = 4;                        // keys per lane
 constexpr int TP_SPAN = TP_BLOCK * TP_ITEMS;       // keys per workgroup of the scan
 constexpr int TP_KEY_RECESSION = 0, TP_KEY_FILL = 1, TP_KEY_FILL_MIRROR = 2;
-
-// the series of flat point k < row[S]: the s with row[s] <= k < row[s+1] (empty series are stepped over)
-__device__ inline int64_t tp_series_of(const int64_t* __restrict__ row, int64_t S, int64_t k) {
-    int64_t lo = 0, hi = S;  // upper_bound of k in row[1 .. S]
-    while (lo < hi) {
-        const int64_t m = lo + ((hi - lo) >> 1);
-        if (row[m + 1] <= k) lo = m + 1;
-        else hi = m;
-    }
-    return lo;
-}
 
 // qac_parameter::is_ok_quality (time_series_dd.h:1463-1471)
 __device__ inline bool tp_ok(double x, double min_x, double max_x) {
@@ -110,7 +100,7 @@ struct tp_rating_args {
 __global__ __launch_bounds__(TP_BLOCK) void tp_rating_kernel(tp_rating_args a) {
     const int64_t stride = int64_t(gridDim.x) * TP_BLOCK;
     for (int64_t k = int64_t(blockIdx.x) * TP_BLOCK + threadIdx.x; k < a.np; k += stride) {
-        const int64_t s = tp_series_of(a.row, a.S, k);
+        const int64_t s = csr_series_of(a.row, a.S, k);
         const int64_t p = a.pack_of[s];
         const int64_t c0 = a.pack_row[p], c1 = a.pack_row[p + 1];
         const int64_t tk = a.t[k];
@@ -166,7 +156,7 @@ struct tp_ice_args {
 __global__ __launch_bounds__(TP_BLOCK) void tp_ice_kernel(tp_ice_args a) {
     const int64_t stride = int64_t(gridDim.x) * TP_BLOCK;
     for (int64_t j = int64_t(blockIdx.x) * TP_BLOCK + threadIdx.x; j < a.nq; j += stride) {
-        const int64_t s = tp_series_of(a.qrow, a.S, j);
+        const int64_t s = csr_series_of(a.qrow, a.S, j);
         const int64_t r0 = a.row[s], n = a.row[s + 1] - r0;
         const int64_t tp_start = n > 0 ? a.t[r0] : 0;  // total_period() of an empty series is [0, 0)
         const int32_t policy = a.policy[s];
@@ -252,7 +242,7 @@ __global__ __launch_bounds__(TP_BLOCK) void tp_scan_block_kernel(tp_scan_args a)
                 if (a.kind == TP_KEY_RECESSION) {
                     if (!(rs_finite(x) && x > 0.5)) key = pos;
                 } else {
-                    if (s < 0 || k < a.row[s] || k >= a.row[s + 1]) s = tp_series_of(a.row, a.S, k);
+                    if (s < 0 || k < a.row[s] || k >= a.row[s + 1]) s = csr_series_of(a.row, a.S, k);
                     if (tp_ok(x, a.min_x[s], a.max_x[s])) key = pos;
                 }
             }
@@ -311,7 +301,7 @@ struct tp_rec_args {
 __global__ __launch_bounds__(TP_BLOCK) void tp_rec_finish_kernel(tp_rec_args a) {
     const int64_t stride = int64_t(gridDim.x) * TP_BLOCK;
     for (int64_t k = int64_t(blockIdx.x) * TP_BLOCK + threadIdx.x; k < a.np; k += stride) {
-        const int64_t s = tp_series_of(a.row, a.S, k);
+        const int64_t s = csr_series_of(a.row, a.S, k);
         const int64_t r0 = a.row[s], r1 = a.row[s + 1];
         const double ice = a.ice[k];
         double r;
@@ -366,7 +356,7 @@ struct tp_fill_args {
 __global__ __launch_bounds__(TP_BLOCK) void tp_fill_finish_kernel(tp_fill_args a) {
     const int64_t stride = int64_t(gridDim.x) * TP_BLOCK;
     for (int64_t k = int64_t(blockIdx.x) * TP_BLOCK + threadIdx.x; k < a.np; k += stride) {
-        const int64_t s = tp_series_of(a.row, a.S, k);
+        const int64_t s = csr_series_of(a.row, a.S, k);
         const int64_t r0 = a.row[s], r1 = a.row[s + 1];
         const double x = a.v[k];
         double r = rs_nan();

@@ -721,6 +721,100 @@ def tsprep_calls(device: int = -1) -> int:
     return int(lib().shyft_hip_tsprep_calls(device))
 
 
+# ---- point-wise filters: convolve_w, derivative, inside, decode (kernels/tsfilter.hip) -------------------------------
+CONVOLVE_USE_FIRST, CONVOLVE_USE_ZERO, CONVOLVE_USE_NAN = 0, 1, 2
+DERIVATIVE_DEFAULT, DERIVATIVE_FORWARD, DERIVATIVE_BACKWARD, DERIVATIVE_CENTER = 0, 1, 2, 3
+TSFILTER_PATH_AUTO, TSFILTER_PATH_DIRECT, TSFILTER_PATH_TILED = 0, 1, 2
+
+
+def ts_convolve_w_csr(row, t, v, t_end, fx, w_row, w, w_of=0, policy=CONVOLVE_USE_FIRST, device: int = -1,
+                      host: bool = False) -> np.ndarray:
+    """S series convolved with weight profiles, one value per point in CSR order (shyft_hip_ts_convolve_w;
+    convolve_w_ts::value, core/time_series.h:966-975): out[i] = sum_j w[j] * x[i-j], the taps added in ascending j,
+    with the policy's stand-in before the first point (CONVOLVE_USE_FIRST x[0], _USE_ZERO 0.0, _USE_NAN NaN). The
+    profiles are a CSR, w_row [W+1] offsets into w; w_of names the profile and policy the policy of each series (one
+    value for all, or [S]). host=True runs the host restatement, which the device is bit-identical to."""
+    S, row, t, v, t_end, fx = _csr_series("ts_convolve_w", row, t, v, t_end, fx)
+    w_row = np.ascontiguousarray(w_row, dtype=np.int64).reshape(-1)
+    w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    W = w_row.shape[0] - 1
+    if W < 0 or w_row[-1] != w.shape[0]:
+        raise ValueError("ts_convolve_w: w_row must end at the number of weights")
+    w_of = _per_series("ts_convolve_w", "w_of", w_of, S, np.int64)
+    policy = _per_series("ts_convolve_w", "policy", policy, S, np.int32)
+    out = np.empty(t.shape[0], dtype=np.float64)
+    fn = lib().shyft_hip_ts_convolve_w_host if host else lib().shyft_hip_ts_convolve_w
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), W, _ptr(w_row), _ptr(w), _ptr(w_of),
+             _ptr(policy), _ptr(out)), None)
+    return out
+
+
+def ts_derivative_csr(row, t, v, t_end, fx, fixed_dt=0, method=DERIVATIVE_DEFAULT, device: int = -1,
+                      host: bool = False) -> np.ndarray:
+    """The derivative of S series, one value per point (shyft_hip_ts_derivative; derivative_ts::values,
+    core/time_series_dd.cpp:311-463): the slope to the next point for a POINT_INSTANT_VALUE series (NaN at the last),
+    the DERIVATIVE_* method's difference for a POINT_AVERAGE_VALUE series. fixed_dt (int64 microseconds) > 0 names
+    the series' even spacing and takes the reference's fixed-step branch, 0 its variable branch; fixed_dt and method
+    are one value for all series or [S]. The result is POINT_AVERAGE_VALUE."""
+    S, row, t, v, t_end, fx = _csr_series("ts_derivative", row, t, v, t_end, fx)
+    fixed_dt = _per_series("ts_derivative", "fixed_dt", fixed_dt, S, np.int64)
+    method = _per_series("ts_derivative", "method", method, S, np.int32)
+    out = np.empty(t.shape[0], dtype=np.float64)
+    fn = lib().shyft_hip_ts_derivative_host if host else lib().shyft_hip_ts_derivative
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), _ptr(fixed_dt), _ptr(method), _ptr(out)), None)
+    return out
+
+
+def ts_inside_csr(row, t, v, t_end, fx, min_x, max_x, nan_x=float("nan"), x_inside=1.0, x_outside=0.0,
+                  device: int = -1, host: bool = False) -> np.ndarray:
+    """S series mapped to x_inside where the value lies in [min_x, max_x) (NaN = no limit), x_outside where not and
+    nan_x where it is not finite, one value per point (shyft_hip_ts_inside; inside_parameter::inside_value,
+    core/time_series_dd.h:1546-1554). The five parameters are one value for all series or [S]."""
+    S, row, t, v, t_end, fx = _csr_series("ts_inside", row, t, v, t_end, fx)
+    p = [_per_series("ts_inside", name, x, S, np.float64)
+         for name, x in (("min_x", min_x), ("max_x", max_x), ("nan_x", nan_x), ("x_inside", x_inside),
+                         ("x_outside", x_outside))]
+    out = np.empty(t.shape[0], dtype=np.float64)
+    fn = lib().shyft_hip_ts_inside_host if host else lib().shyft_hip_ts_inside
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), *(_ptr(x) for x in p), _ptr(out)), None)
+    return out
+
+
+def ts_decode_csr(row, t, v, t_end, fx, start_bit, n_bits, device: int = -1, host: bool = False) -> np.ndarray:
+    """n_bits bits from start_bit of the values of S series taken as unsigned integers, one value per point; NaN for a
+    value that is not finite, negative or above 2^52 (shyft_hip_ts_decode; bit_decoder::decode,
+    core/time_series_dd.h:1650-1655). start_bit and n_bits are one value for all series or [S]."""
+    S, row, t, v, t_end, fx = _csr_series("ts_decode", row, t, v, t_end, fx)
+    start_bit = _per_series("ts_decode", "start_bit", start_bit, S, np.int32)
+    n_bits = _per_series("ts_decode", "n_bits", n_bits, S, np.int32)
+    out = np.empty(t.shape[0], dtype=np.float64)
+    fn = lib().shyft_hip_ts_decode_host if host else lib().shyft_hip_ts_decode
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), _ptr(start_bit), _ptr(n_bits), _ptr(out)), None)
+    return out
+
+
+def tsfilter_last_ms(device: int = -1) -> float:
+    """HIP-event milliseconds of the kernel of the last ts_convolve_w_csr, ts_derivative_csr, ts_inside_csr or
+    ts_decode_csr device call on the device, copies excluded."""
+    return float(lib().shyft_hip_tsfilter_last_ms(device))
+
+
+def tsfilter_calls(device: int = -1) -> int:
+    """The number of those device calls that launched on the device so far."""
+    return int(lib().shyft_hip_tsfilter_calls(device))
+
+
+def tsfilter_set_path(path: int) -> None:
+    """TSFILTER_PATH_DIRECT or TSFILTER_PATH_TILED forces the launch shape of ts_convolve_w_csr for the process,
+    TSFILTER_PATH_AUTO gives the choice back (test and measurement aid)."""
+    check(lib().shyft_hip_tsfilter_set_path(int(path)), None)
+
+
+def tsfilter_last_path(device: int = -1) -> int:
+    """TSFILTER_PATH_DIRECT or TSFILTER_PATH_TILED: the launch shape of the last ts_convolve_w_csr on the device."""
+    return int(lib().shyft_hip_tsfilter_last_path(device))
+
+
 # ---- forecast skill by lead time (kernels/forecast.hip) ---------------------------------------------------------------
 def forecast_skill_csr(row, t, v, t_end, fx, fc_row, fc_ix, obs_ix, t0_offset, dt, n, device: int = -1,
                        host: bool = False, slices: bool = False):
