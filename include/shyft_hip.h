@@ -651,6 +651,65 @@ int shyft_hip_forecast_skill_host(int device, size_t S, const int64_t* row, cons
 double shyft_hip_forecast_skill_last_ms(int device);
 uint64_t shyft_hip_forecast_skill_calls(int device);
 
+/* ---- KRLS interpolation (prediction::krls_rbf_predictor, core/predictions.h:30-343, over dlib::krls;
+ * krls_interpolation_ts, core/time_series_dd.h:1368-1442) ----
+ * The algorithm is restated from its published form (Engel, Mannor, Meir 2004, eqs. 3.12-3.16) in host/krls.hpp;
+ * last-bit parity with dlib is not pinned. A predictor's state is its dictionary d [m] of sample positions, the weights
+ * alpha [m] and the dense row-major matrices Kinv and P [m][m].
+ *
+ * shyft_hip_krls_train_csr replaces one krls_rbf_predictor::train call (predictions.h:139-181) per series: the S series
+ * in the CSR form of shyft_hip_resample, each with its own predictor parameters dt (int64 microseconds), gamma, tolerance,
+ * max_dict (the predictor's size), and its own offset, count (< 0: to the end), stride, iterations and mse_tol, all [S].
+ * s_row [S+1] (null: every predictor starts empty) gives the starting dictionaries s_d, s_alpha [s_row[S]] and the dense
+ * starting matrices s_Kinv, s_P, one after the other (sum of m^2 doubles), so that a trained predictor is trained
+ * further. One workgroup trains one series: with both matrices in LDS while the dictionary stays within
+ * SHYFT_HIP_KRLS_LDS_CAPACITY entries, in a device-memory workspace up to SHYFT_HIP_KRLS_MAX_DICT, and with
+ * host/krls.hpp beyond that or when the dictionary reaches max_dict (the removal of an entry is host only). *result
+ * holds the trained states; read it with shyft_hip_krls_result_sizes (d_row [S+1]) and shyft_hip_krls_result_fetch
+ * (d, alpha [d_row[S]]; Kinv, P [sum of m^2]; mse [S] as train returns it; path [S] SHYFT_HIP_KRLS_PATH_*) and release
+ * it with shyft_hip_krls_result_free. A batch whose workspace exceeds the free device memory is refused.
+ * shyft_hip_krls_train_csr_host trains every series with host/krls.hpp (path HOST); the device is bit-identical to it. */
+#define SHYFT_HIP_KRLS_LDS_CAPACITY 99
+#define SHYFT_HIP_KRLS_LDS_SMALL_CAPACITY 31 /* tried first: a storage small enough for eight workgroups per CU */
+#define SHYFT_HIP_KRLS_MAX_DICT 1024
+#define SHYFT_HIP_KRLS_PATH_LDS 1
+#define SHYFT_HIP_KRLS_PATH_WORKSPACE 2
+#define SHYFT_HIP_KRLS_PATH_HOST 3
+typedef struct shyft_hip_krls_result shyft_hip_krls_result;
+int shyft_hip_krls_train_csr(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                             const int64_t* t_end, const int32_t* fx, const int64_t* dt, const double* gamma,
+                             const double* tolerance, const int64_t* max_dict, const int64_t* offset, const int64_t* count,
+                             const int64_t* stride, const int64_t* iterations, const double* mse_tol, const int64_t* s_row,
+                             const double* s_d, const double* s_alpha, const double* s_Kinv, const double* s_P,
+                             shyft_hip_krls_result** result);
+int shyft_hip_krls_train_csr_host(int device, size_t S, const int64_t* row, const int64_t* t, const double* v,
+                                  const int64_t* t_end, const int32_t* fx, const int64_t* dt, const double* gamma,
+                                  const double* tolerance, const int64_t* max_dict, const int64_t* offset,
+                                  const int64_t* count, const int64_t* stride, const int64_t* iterations,
+                                  const double* mse_tol, const int64_t* s_row, const double* s_d, const double* s_alpha,
+                                  const double* s_Kinv, const double* s_P, shyft_hip_krls_result** result);
+int shyft_hip_krls_result_sizes(const shyft_hip_krls_result* result, size_t S, int64_t* d_row);
+int shyft_hip_krls_result_fetch(const shyft_hip_krls_result* result, size_t S, double* d, double* alpha, double* Kinv,
+                                double* P, double* mse, int32_t* path);
+void shyft_hip_krls_result_free(shyft_hip_krls_result* result);
+/* krls_rbf_predictor::predict_vec (predictions.h:193-207) of S predictors in one launch: predictor s, given by its
+ * dictionary and weights (d_row [S+1], d, alpha), dt and gamma [S], evaluated at its output times q_t[q_row[s] ..
+ * q_row[s+1]) (int64 microseconds): out = sum_i alpha_i * k(x, d_i) in index order, 0.0 for an empty dictionary. With
+ * q_v (one value per output time) out is the residual q_v - f(x), NaN where q_v is NaN: the terms that predictor_mse
+ * (:253-282) and mse_ts (:300-334) square and sum. The _host twin evaluates the same with host/krls.hpp. */
+int shyft_hip_krls_predict(int device, size_t S, const int64_t* d_row, const double* d, const double* alpha,
+                           const int64_t* dt, const double* gamma, const int64_t* q_row, const int64_t* q_t,
+                           const double* q_v, double* out);
+int shyft_hip_krls_predict_host(int device, size_t S, const int64_t* d_row, const double* d, const double* alpha,
+                                const int64_t* dt, const double* gamma, const int64_t* q_row, const int64_t* q_t,
+                                const double* q_v, double* out);
+/* HIP-event milliseconds of the kernels of the last shyft_hip_krls_train_csr (all its launches) or shyft_hip_krls_predict
+ * on this device, copies excluded. (No reference counterpart: measurement and test aid.) */
+double shyft_hip_krls_last_ms(int device);
+/* SHYFT_HIP_KRLS_PATH_WORKSPACE makes shyft_hip_krls_train_csr skip the LDS storage for the process, 0 gives the
+ * choice back. (Measurement aid: the two storages at equal dictionary size.) */
+int shyft_hip_krls_set_path(int path);
+
 size_t shyft_hip_number_of_catchments(const shyft_hip_region* h);
 int shyft_hip_catchment_ids(const shyft_hip_region* h, int64_t* cids);
 

@@ -113,6 +113,15 @@ SIGNATURES = {
                                       + [C.c_void_p] * 9),
     "shyft_hip_forecast_skill_last_ms": (C.c_double, [C.c_int]),
     "shyft_hip_forecast_skill_calls": (C.c_uint64, [C.c_int]),
+    "shyft_hip_krls_train_csr": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 19 + [C.POINTER(C.c_void_p)]),
+    "shyft_hip_krls_train_csr_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 19 + [C.POINTER(C.c_void_p)]),
+    "shyft_hip_krls_result_sizes": (C.c_int, [_h, C.c_size_t, C.c_void_p]),
+    "shyft_hip_krls_result_fetch": (C.c_int, [_h, C.c_size_t] + [C.c_void_p] * 6),
+    "shyft_hip_krls_result_free": (None, [_h]),
+    "shyft_hip_krls_predict": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 9),
+    "shyft_hip_krls_predict_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 9),
+    "shyft_hip_krls_last_ms": (C.c_double, [C.c_int]),
+    "shyft_hip_krls_set_path": (C.c_int, [C.c_int]),
     "shyft_hip_synthetic_elevation": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]),
     "shyft_hip_run_cells": (C.c_int, [_h, C.c_size_t, C.c_int, C.c_int]),
     "shyft_hip_run_cells_async": (C.c_int, [_h, C.c_int, C.c_int]),

@@ -35,6 +35,8 @@ from ._tsprep import (  # noqa: F401  (re-exported names)
 
 from . import _tsfilter
 from ._tsfilter import convolve_policy, derivative_method  # noqa: F401  (re-exported names)
+from . import _krls
+from ._krls import KrlsRbfPredictor  # noqa: F401  (re-exported name)
 
 USE_FIRST, USE_ZERO, USE_NAN = convolve_policy.USE_FIRST, convolve_policy.USE_ZERO, convolve_policy.USE_NAN
 DEFAULT, FORWARD, BACKWARD, CENTER = (derivative_method.DEFAULT, derivative_method.FORWARD, derivative_method.BACKWARD,
@@ -260,6 +262,17 @@ class TimeSeries:
         negative or above 2^52 (decode_ts, time_series_dd.h:1609-1700); the source's point type"""
         return _tsfilter.decode([self], start_bit, n_bits, True)[0]
 
+    # KRLS interpolation (api_time_series.cpp:876-991; time_series_dd.cpp:744-753), one series on the host
+    def krls_interpolation(self, dt, gamma=1e-3, tolerance=0.01, size=1000000):
+        """this series smoothed and gap-filled: the predictions, at its own points, of a KrlsRbfPredictor(dt, gamma,
+        tolerance, size) trained once over it (krls_interpolation_ts, time_series_dd.h:1368-1442); the source's time
+        axis and point type"""
+        return _krls.krls_interpolation([self], dt, gamma, tolerance, size, True)[0]
+
+    def get_krls_predictor(self, dt, gamma=1e-3, tolerance=0.01, size=1000000):
+        """a KrlsRbfPredictor(dt, gamma, tolerance, size) trained once over this series"""
+        return _krls.get_krls_predictors([self], dt, gamma, tolerance, size, True)[0]
+
     # arithmetic (time_series_dd.cpp:94-122, 922-928): every result is a lazy expression, the other operand a
     # TimeSeries or a number. Nothing is computed until the result is read or evaluated.
     def __add__(self, o):
@@ -478,6 +491,15 @@ class TsVector(_Vector):
 
     def decode(self, start_bit, n_bits, *, host=False):
         return _tsfilter.decode(self, start_bit, n_bits, host)
+
+    # KRLS interpolation of every series (this project's batch forms): the whole vector is trained in one device call
+    # and predicted in a second; each parameter is one value for all series or one per series
+    def krls_interpolation(self, dt, gamma=1e-3, tolerance=0.01, size=1000000, *, host=False):
+        return _krls.krls_interpolation(self, dt, gamma, tolerance, size, host)
+
+    def get_krls_predictors(self, dt, gamma=1e-3, tolerance=0.01, size=1000000, *, host=False):
+        """one trained KrlsRbfPredictor per series, as a list"""
+        return _krls.get_krls_predictors(self, dt, gamma, tolerance, size, host)
 
     # forecast skill by lead time and the forecast merge (time_series_dd.cpp:1120-1165, api_time_series.cpp:299-339)
     def average_slice(self, lead_time, delta_t, n, *, host=False):

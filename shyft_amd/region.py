@@ -895,3 +895,112 @@ def ts_expr_last_ms(device: int = -1) -> float:
 def ts_expr_calls(device: int = -1) -> int:
     """The number of ts_expr_csr device calls that launched on the device so far."""
     return int(lib().shyft_hip_ts_expr_calls(device))
+
+
+# ---- KRLS interpolation (kernels/krls.hip) ------------------------------------------------------------------------------
+KRLS_LDS_CAPACITY, KRLS_MAX_DICT = 99, 1024  # SHYFT_HIP_KRLS_LDS_CAPACITY, SHYFT_HIP_KRLS_MAX_DICT
+KRLS_LDS_SMALL_CAPACITY = 31                 # SHYFT_HIP_KRLS_LDS_SMALL_CAPACITY: the LDS storage tried first
+KRLS_PATH_LDS, KRLS_PATH_WORKSPACE, KRLS_PATH_HOST = 1, 2, 3
+KRLS_DEFAULT_SIZE = 1000000
+
+
+def krls_train_csr(row, t, v, t_end, fx, dt, gamma=1e-3, tolerance=0.01, size=KRLS_DEFAULT_SIZE, offset=0, count=-1,
+                   stride=1, iterations=1, mse_tol=0.001, state=None, device: int = -1, host: bool = False):
+    """One KRLS predictor trained per series, all in one device call (shyft_hip_krls_train_csr;
+    krls_rbf_predictor::train, core/predictions.h:139-181, restated in csrc/host/krls.hpp). The S series are in the CSR
+    form of resample_csr. dt (int64 microseconds), gamma, tolerance, size (the most dictionary entries), offset, count
+    (< 0: to the end), stride, iterations and mse_tol are one value for all series or [S]. state = (d_row, d, alpha,
+    Kinv, P), as this function returns it, trains trained predictors further; None starts empty ones.
+    Returns (d_row, d, alpha, Kinv, P, mse, path): d_row [S+1] offsets of the dictionaries d (sample positions) and
+    weights alpha, Kinv and P lists of S dense [m][m] arrays, mse [S] as train returns it, and path [S]: KRLS_PATH_LDS
+    (both matrices in LDS, at most KRLS_LDS_CAPACITY entries), KRLS_PATH_WORKSPACE (device memory, at most
+    KRLS_MAX_DICT) or KRLS_PATH_HOST (a longer dictionary, or one that reached `size` and had an entry removed).
+    host=True trains every series with the host restatement, which the device is bit-identical to."""
+    S, row, t, v, t_end, fx = _csr_series("krls_train", row, t, v, t_end, fx)
+    dt = _per_series("krls_train", "dt", dt, S, np.int64)
+    gamma = _per_series("krls_train", "gamma", gamma, S, np.float64)
+    tolerance = _per_series("krls_train", "tolerance", tolerance, S, np.float64)
+    size = _per_series("krls_train", "size", size, S, np.int64)
+    offset = _per_series("krls_train", "offset", offset, S, np.int64)
+    count = _per_series("krls_train", "count", count, S, np.int64)
+    stride = _per_series("krls_train", "stride", stride, S, np.int64)
+    iterations = _per_series("krls_train", "iterations", iterations, S, np.int64)
+    mse_tol = _per_series("krls_train", "mse_tol", mse_tol, S, np.float64)
+    s_row = s_d = s_alpha = s_K = s_P = None
+    if state is not None:
+        s_row = np.ascontiguousarray(state[0], dtype=np.int64).reshape(-1)
+        s_d = np.ascontiguousarray(state[1], dtype=np.float64).reshape(-1)
+        s_alpha = np.ascontiguousarray(state[2], dtype=np.float64).reshape(-1)
+        if s_row.shape[0] != S + 1 or s_row[0] != 0 or s_row[-1] != s_d.shape[0] or s_alpha.shape[0] != s_d.shape[0] \
+                or len(state[3]) != S or len(state[4]) != S:
+            raise ValueError("krls_train: the starting state must hold one predictor per series")
+        mats = []
+        for M in (state[3], state[4]):
+            dense = [np.ascontiguousarray(x, dtype=np.float64) for x in M]
+            if any(x.shape != (s_row[k + 1] - s_row[k],) * 2 for k, x in enumerate(dense)):
+                raise ValueError("krls_train: a starting matrix is not [m][m]")
+            mats.append(np.concatenate([x.reshape(-1) for x in dense]) if dense else np.empty(0))
+        s_K, s_P = mats
+    res = C.c_void_p()
+    fn = lib().shyft_hip_krls_train_csr_host if host else lib().shyft_hip_krls_train_csr
+    check(fn(device, S, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), _ptr(dt), _ptr(gamma), _ptr(tolerance),
+             _ptr(size), _ptr(offset), _ptr(count), _ptr(stride), _ptr(iterations), _ptr(mse_tol), _ptr(s_row), _ptr(s_d),
+             _ptr(s_alpha), _ptr(s_K), _ptr(s_P), C.byref(res)), None)
+    try:
+        d_row = np.zeros(S + 1, dtype=np.int64)
+        check(lib().shyft_hip_krls_result_sizes(res, S, _ptr(d_row)), None)
+        m = np.diff(d_row)
+        d = np.empty(int(d_row[-1]), dtype=np.float64)
+        alpha = np.empty_like(d)
+        K = np.empty(int((m * m).sum()), dtype=np.float64)
+        P = np.empty_like(K)
+        mse = np.empty(S, dtype=np.float64)
+        path = np.empty(S, dtype=np.int32)
+        check(lib().shyft_hip_krls_result_fetch(res, S, _ptr(d), _ptr(alpha), _ptr(K), _ptr(P), _ptr(mse), _ptr(path)), None)
+    finally:
+        lib().shyft_hip_krls_result_free(res)
+    m_off = np.concatenate([[0], np.cumsum(m * m)]).astype(np.int64)
+    Ks = [K[m_off[k]:m_off[k + 1]].reshape(m[k], m[k]) for k in range(S)]
+    Ps = [P[m_off[k]:m_off[k + 1]].reshape(m[k], m[k]) for k in range(S)]
+    return d_row, d, alpha, Ks, Ps, mse, path
+
+
+def krls_predict(d_row, d, alpha, dt, gamma, q_row, q_t, q_v=None, device: int = -1, host: bool = False) -> np.ndarray:
+    """S trained predictors evaluated at output times of their own CSR (q_row [S+1], q_t int64 microseconds), one value
+    per output time (shyft_hip_krls_predict; krls_rbf_predictor::predict_vec, core/predictions.h:193-207):
+    sum_i alpha_i * k(x, d_i) in index order, 0.0 for an empty dictionary. With q_v, one value per output time, the
+    result is the residual q_v - f(x), NaN where q_v is NaN (the terms of predictor_mse and mse_ts). dt and gamma are
+    one value for all predictors or [S]. host=True runs the host restatement, which the device is bit-identical to."""
+    d_row = np.ascontiguousarray(d_row, dtype=np.int64).reshape(-1)
+    d = np.ascontiguousarray(d, dtype=np.float64).reshape(-1)
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+    q_row = np.ascontiguousarray(q_row, dtype=np.int64).reshape(-1)
+    q_t = np.ascontiguousarray(q_t, dtype=np.int64).reshape(-1)
+    S = d_row.shape[0] - 1
+    if S < 0 or q_row.shape[0] != S + 1 or d.shape[0] != alpha.shape[0]:
+        raise ValueError("krls_predict: d_row and q_row must have one entry more than there are predictors")
+    if S and (d_row[0] != 0 or d_row[-1] != d.shape[0] or q_row[0] != 0 or q_row[-1] != q_t.shape[0]):
+        raise ValueError("krls_predict: d_row must run over the dictionaries and q_row over the output times")
+    if q_v is not None:
+        q_v = np.ascontiguousarray(q_v, dtype=np.float64).reshape(-1)
+        if q_v.shape[0] != q_t.shape[0]:
+            raise ValueError("krls_predict: q_v must hold one value per output time")
+    dt = _per_series("krls_predict", "dt", dt, S, np.int64)
+    gamma = _per_series("krls_predict", "gamma", gamma, S, np.float64)
+    out = np.empty(q_t.shape[0] if S else 0, dtype=np.float64)
+    fn = lib().shyft_hip_krls_predict_host if host else lib().shyft_hip_krls_predict
+    check(fn(device, S, _ptr(d_row), _ptr(d), _ptr(alpha), _ptr(dt), _ptr(gamma), _ptr(q_row), _ptr(q_t), _ptr(q_v),
+             _ptr(out)), None)
+    return out
+
+
+def krls_last_ms(device: int = -1) -> float:
+    """HIP-event milliseconds of the kernels of the last krls_train_csr (all its launches) or krls_predict device call
+    on the device, copies excluded."""
+    return float(lib().shyft_hip_krls_last_ms(device))
+
+
+def krls_set_path(path: int) -> None:
+    """KRLS_PATH_WORKSPACE makes krls_train_csr skip the LDS storage for the process, 0 gives the choice back
+    (measurement aid)."""
+    check(lib().shyft_hip_krls_set_path(int(path)), None)
