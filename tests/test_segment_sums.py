@@ -7,28 +7,9 @@ import numpy as np
 import pytest
 
 from shyft_amd import synthetic
+from tests.reduce_cases import device_order_sum
 
 pytestmark = pytest.mark.gpu
-
-RB = 256
-
-
-def device_order_sum(vals):
-    """The segment-sum kernel's reduction of one segment's values (in segment order)."""
-    acc = [0.0] * RB
-    for k, v in enumerate(vals.tolist()):
-        acc[k % RB] += v
-    w = np.array(acc).reshape(RB // 64, 64)
-    lanes = np.arange(64)
-    off = 32
-    while off:
-        w = w + w[:, lanes ^ off]
-        off >>= 1
-    part = w[:, 0]
-    r = part[0]
-    for p in part[1:]:
-        r = r + p
-    return r
 
 
 def expected(series, groups, order):

@@ -1,7 +1,9 @@
 """Catchment statistics on the GPU (cell_statistics, core/cell_model.h:194-406;
 region_model::catchment_discharges, core/region_model.h:873-885) against numpy
 sums over the same per-cell series. The GPU reduces in a fixed tree order,
-the reference sums sequentially in cell order: tolerance 1e-13 relative."""
+the reference sums sequentially in cell order: tolerance 1e-13 relative.
+The order of the additions itself, the segment and selection size classes and the special values are pinned bit for
+bit against a plain restatement of the kernels in tests/test_stats_edges.py."""
 import numpy as np
 import pytest
 
