@@ -37,7 +37,7 @@ def load(variant: str = "detmath"):
     if not os.path.exists(path):
         build()
     L = C.CDLL(path)
-    for fn in ("oracle_exp", "oracle_log", "oracle_lgamma_fn"):
+    for fn in ("oracle_exp", "oracle_log", "oracle_lgamma_fn", "oracle_pow4", "oracle_pow8"):
         getattr(L, fn).restype = _d
         getattr(L, fn).argtypes = [_d]
     L.oracle_pow.restype = _d
