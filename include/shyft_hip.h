@@ -450,6 +450,55 @@ uint64_t shyft_hip_resample_calls(int device);
 int shyft_hip_resample_set_path(int path);
 int shyft_hip_resample_last_path(int device);
 
+/* Percentiles of a vector of point series on the fixed_dt axis (ta_t0, ta_dt, T) in one fused launch of
+ * kernels/ts_percentiles.hip on a device (device < 0 = current): calculate_percentiles with skip_nans = true
+ * (core/time_series_statistics.h:184-246), which api.percentiles binds (api_time_series.cpp:1299). It replaces one
+ * average_accessor per series (core/time_series.h:2033-2072), the sample sort of every interval
+ * (time_series_statistics.h:115-160) and the extract_statistic_from_vector passes (:41-90, :221-226). Host pointers,
+ * stateless. The R stored series are in the CSR form of shyft_hip_resample (row [R+1], t and v [row[R]], t_end [R],
+ * fx [R]). The vector has S views: view s is stored series src[s] in [0, R) with every point time and its t_end moved
+ * by shift[s] microseconds (time_shift_ts, core/time_series_dd.h:707-751), so the partitions of one record
+ * (ts.partition_by, core/time_series.h:2451-2494, time_series_dd.cpp:653-663) share one stored copy. The sample of
+ * (view, interval) is mode AVERAGE of shyft_hip_resample on the moved series; non-finite samples are dropped. pct[k]:
+ *   0..100   the R7 percentile with the reference's eps = 1e-30 rules (:133-153),
+ *   -1       AVERAGE: the sorted samples added in sorted order, over their count (:127-132),
+ *   -1000 / +1000  MIN_EXTREME / MAX_EXTREME: nan_min / nan_max (:24-39) folded over the values of the points whose
+ *            moved times lie inside the interval, across all views; not an order statistic of the averages,
+ *   anything else, or an interval without a finite sample: NaN.
+ * out is [n_pct][T]. Checked before any work with the texts of shyft_hip_resample: increasing times, t_end after the
+ * last point, ta_dt > 0, the one-point-series refusal (on the moved series); src[s] out of range is an error that
+ * names the view. S == 0, T == 0 or n_pct == 0 returns 0 and launches nothing. n_pct above SHYFT_HIP_PERCENTILES_MAX
+ * or S above SHYFT_HIP_TS_PERCENTILES_MAX_SERIES is refused on the device, the text naming the limit. Every entry,
+ * AVERAGE included, is bit-identical to shyft_hip_ts_percentiles_host; the sign of a zero result is unspecified (+0.0
+ * and -0.0 compare equal in a sort and in min / max). */
+#define SHYFT_HIP_TS_PERCENTILES_MAX_SERIES 4096
+int shyft_hip_ts_percentiles(int device, size_t R, const int64_t* row, const int64_t* t, const double* v,
+                             const int64_t* t_end, const int32_t* fx, size_t S, const int32_t* src,
+                             const int64_t* shift, int64_t ta_t0, int64_t ta_dt, size_t T, const int64_t* pct,
+                             size_t n_pct, double* out);
+/* The same values from host/ts_percentiles.hpp, the restatement of time_series_statistics.h:24-90, 115-160 and
+ * 184-246 over average_values of host/time_series.hpp; no device call, `device` is not used, S and n_pct are not
+ * limited. */
+int shyft_hip_ts_percentiles_host(int device, size_t R, const int64_t* row, const int64_t* t, const double* v,
+                                  const int64_t* t_end, const int32_t* fx, size_t S, const int32_t* src,
+                                  const int64_t* shift, int64_t ta_t0, int64_t ta_dt, size_t T, const int64_t* pct,
+                                  size_t n_pct, double* out);
+/* HIP-event milliseconds of the kernel of the last shyft_hip_ts_percentiles on this device (device < 0 = current),
+ * copies excluded. (No reference counterpart: measurement only.) */
+double shyft_hip_ts_percentiles_last_ms(int device);
+/* The number of shyft_hip_ts_percentiles calls that launched on this device so far. (No reference counterpart: test
+ * aid.) */
+uint64_t shyft_hip_ts_percentiles_calls(int device);
+/* The launch shape: WAVE, one wavefront per interval, one view per lane, the keys sorted across the lanes (S <= 64);
+ * LDS, one workgroup per interval, the keys sorted in LDS. AUTO takes WAVE up to 64 views and LDS above. A forced
+ * WAVE with more than 64 views is an error. set_path is process-wide; last_path reports what the last call on the
+ * device ran. (No reference counterpart: test and measurement aid.) */
+#define SHYFT_HIP_TS_PERCENTILES_PATH_AUTO 0
+#define SHYFT_HIP_TS_PERCENTILES_PATH_WAVE 1
+#define SHYFT_HIP_TS_PERCENTILES_PATH_LDS 2
+int shyft_hip_ts_percentiles_set_path(int path);
+int shyft_hip_ts_percentiles_last_path(int device);
+
 /* Observation preparation of S point series in one device call each (kernels/tsprep.hip; device < 0 = current). Host
  * pointers, stateless. The series are in the CSR form of shyft_hip_resample (row [S+1], t and v [row[S]], t_end [S],
  * fx [S]) and are checked in the same way and with the same texts before anything is launched: row[0] == 0 and

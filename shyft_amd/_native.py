@@ -78,6 +78,15 @@ SIGNATURES = {
     "shyft_hip_resample_calls": (C.c_uint64, [C.c_int]),
     "shyft_hip_resample_set_path": (C.c_int, [C.c_int]),
     "shyft_hip_resample_last_path": (C.c_int, [C.c_int]),
+    "shyft_hip_ts_percentiles": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 2
+                                 + [C.c_int64, C.c_int64, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "shyft_hip_ts_percentiles_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t]
+                                      + [C.c_void_p] * 2
+                                      + [C.c_int64, C.c_int64, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "shyft_hip_ts_percentiles_last_ms": (C.c_double, [C.c_int]),
+    "shyft_hip_ts_percentiles_calls": (C.c_uint64, [C.c_int]),
+    "shyft_hip_ts_percentiles_set_path": (C.c_int, [C.c_int]),
+    "shyft_hip_ts_percentiles_last_path": (C.c_int, [C.c_int]),
     "shyft_hip_ts_rating_curve": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 6),
     "shyft_hip_ts_rating_curve_host": (C.c_int, [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.c_size_t]
                                        + [C.c_void_p] * 6),

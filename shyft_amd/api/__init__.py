@@ -74,6 +74,83 @@ class Calendar:
         import datetime
         return datetime.datetime.fromtimestamp(t, datetime.timezone.utc).timetuple().tm_yday
 
+    # calendar arithmetic (utctime_utilities.cpp:281-366) for the UTC zone, where every utc offset is 0
+    QUARTER, WEEK, HOUR_3, MINUTE, SECOND = 3 * 30 * 86400, 7 * 86400, 3 * 3600, 60, 1
+
+    @staticmethod
+    def _calendar_units(t):
+        """(year, month, day, seconds into the day) of t"""
+        days, rest = divmod(t, 86400)
+        z = int(days) + 719468
+        era = z // 146097
+        doe = z - era * 146097
+        yoe = (doe - doe // 1460 + doe // 36524 - doe // 146096) // 365
+        doy = doe - (365 * yoe + yoe // 4 - yoe // 100)
+        mp = (5 * doy + 2) // 153
+        m = mp + 3 if mp < 10 else mp - 9
+        return yoe + era * 400 + (m <= 2), m, doy - (153 * mp + 2) // 5 + 1, rest
+
+    def _time_of(self, year, month, day, rest):
+        return self.time(year, month, day) + rest
+
+    def add(self, t, dt, n):
+        """t plus n units of dt (calendar::add, :281-319): YEAR, QUARTER and MONTH step the calendar fields, any
+        other dt is plain t + n * dt."""
+        n = int(n)
+        span = n * dt
+        trunc = lambda a, b: int(abs(a) // b) * (1 if a >= 0 else -1)  # noqa: E731  (C++ division rounds towards zero)
+        if dt == Calendar.YEAR:
+            y, m, d, rest = self._calendar_units(t)
+            return self._time_of(y + trunc(span, Calendar.YEAR), m, d, rest)
+        if dt in (Calendar.QUARTER, Calendar.MONTH):
+            if dt == Calendar.QUARTER:  # it appears as 3 x MONTH
+                n = 3 * n
+            y, m, d, rest = self._calendar_units(t)
+            n_years = trunc(trunc(span, Calendar.MONTH), 12)
+            y += n_years
+            m += n - n_years * 12  # the remaining months, then repair under- or overflow
+            if m < 1:
+                m, y = m + 12, y - 1
+            elif m > 12:
+                m, y = m - 12, y + 1
+            return self._time_of(y, m, d, rest)
+        return t + span
+
+    def _diff_units(self, t1, t2, dt):
+        """(n, remainder) of calendar::diff_units (:321-366): the whole units of dt from t1 to t2, complementary to
+        add, and what is left after them"""
+        if dt == 0:
+            return 0, 0
+        sgn = 1
+        if t1 > t2:
+            sgn, t1, t2 = -1, t2, t1
+        n = int((t2 - t1) // dt)  # a rough estimate for MONTH, QUARTER and YEAR
+        if dt < Calendar.DAY:
+            rem = t2 - self.add(t1, dt, n) if dt > Calendar.HOUR else t2 - (t1 + n * dt)
+            return n * sgn, rem
+        if dt == Calendar.MONTH:
+            n -= n // 72  # MONTH is 30 days, a real one about 30.4375: one month too many after 72
+        elif dt == Calendar.QUARTER:
+            n -= n // (3 * 72)
+        elif dt == Calendar.YEAR:
+            n -= n // (4 * 365 * 365)
+        t2x = self.add(t1, dt, n)
+        if t2x > t2:  # one step too far
+            n -= 1
+            rem = t2 - self.add(t1, dt, n)
+        elif t2x < t2:  # one step short, maybe
+            t2xx = self.add(t1, dt, n + 1)
+            if t2xx > t2:
+                rem = t2 - t2x
+            else:
+                n, rem = n + 1, t2 - t2xx
+        else:
+            rem = 0
+        return n * sgn, rem
+
+    def diff_units(self, t1, t2, dt):
+        return self._diff_units(t1, t2, dt)[0]
+
 
 class UtcPeriod:
     def __init__(self, start, end):
@@ -151,17 +228,30 @@ class TimeSeries:
 
     # An arithmetic result holds an expression tree (_expr, with its point type _fx) and no series (_impl) until it
     # is read: _ts evaluates the tree on the host on first read and keeps the result. A concrete series has no tree.
-    _impl = _expr = _fx = None
+    # A partition (partition_by) is a shifted view, (_view_of, _view_shift): a source `_PointTs` seen some seconds
+    # later. It has no series of its own until _ts is read; api.percentiles reads the pair instead.
+    _impl = _expr = _fx = _view_of = None
+    _view_shift = 0
 
     @property
     def _ts(self):
         if self._impl is None:
-            _ts_expr.evaluate([self], host=True)
+            if self._view_of is not None:
+                self._ts = self._view_of._shifted(self._view_shift)
+            else:
+                _ts_expr.evaluate([self], host=True)
         return self._impl
 
     @_ts.setter
     def _ts(self, impl):
-        self._impl, self._expr = impl, None
+        self._impl, self._expr, self._view_of = impl, None, None
+
+    @staticmethod
+    def _shifted_view(source, shift):
+        """the `_PointTs` source seen shift seconds later, not materialised"""
+        ts = TimeSeries.__new__(TimeSeries)
+        ts._view_of, ts._view_shift = source, shift
+        return ts
 
     def value(self, i):
         return self._ts.value(i)
@@ -183,9 +273,16 @@ class TimeSeries:
         return self._ts.time(i)
 
     def point_interpretation(self):
-        if self._impl is None:  # an expression answers from its tree, without evaluating
-            return self._fx
+        if self._impl is None:  # a view and an expression answer without evaluating
+            return self._view_of.point_interpretation() if self._view_of is not None else self._fx
         return self._ts.point_interpretation()
+
+    def index_of(self, t):
+        """the index of the interval that holds t, -1 outside the series (point_ts::index_of, time_series.h:343;
+        time_shift_ts::index_of, time_series_dd.h:742)"""
+        if self._impl is None and self._view_of is not None:
+            return self._view_of.index_of(t - self._view_shift)
+        return self._ts.index_of(t)
 
     def total_period(self):
         return UtcPeriod(*self._ts.total_period())
@@ -318,6 +415,22 @@ class TimeSeries:
         """this series dt seconds later (time_shift_ts, time_series_dd.h:707-751)"""
         return _ts_expr.shifted(self, dt)
 
+    def partition_by(self, calendar, t, partition_interval, n_partitions, common_t0):
+        """n_partitions pieces of this series, piece i starting calendar.add(t, partition_interval, i), all moved to
+        start at common_t0 (apoint_ts::partition_by, time_series_dd.cpp:653-663; core/time_series.h:2451-2494): a
+        TsVector whose element i is this series shifted by common_t0 - calendar.add(t, partition_interval, i). The
+        elements are shifted views of one stored series; api.percentiles takes them as they are, anything else that
+        reads one makes it a concrete series first."""
+        if n_partitions < 1:
+            raise RuntimeError("n_partitions should be > 0")
+        if partition_interval <= 0:
+            raise RuntimeError("partition_interval should be > 0, typically Calendar::YEAR|MONTH|WEEK|DAY")
+        if calendar._diff_units(t, common_t0, partition_interval)[1] != 0:
+            raise RuntimeError("t0 must align with a complete calendar multiple dt from t")
+        source = self._ts
+        return TsVector(TimeSeries._shifted_view(source, common_t0 - calendar.add(t, partition_interval, i))
+                        for i in range(int(n_partitions)))
+
     def evaluate(self, *, host=False):
         """the concrete series of this expression: one device call, or with host=True the host restatement,
         bit-identical. The result is kept, so reading this series afterwards computes nothing."""
@@ -372,66 +485,56 @@ class statistics_property:  # time_series_statistics.h:107-111
     MAX_EXTREME = 1000
 
 
-def _extract_statistics(ts, ta, fx):
-    """extract_statistics (time_series_statistics.h:41-75): fx folded over the points of ts inside each interval of ta."""
-    times, vals = ts._ts._times, ts._ts._values
-    n = len(times)
-    t_first = ta.time(0) if ta.size() else 0.0
-    i_s = None  # make_time_axis_map(ts.time_axis(), ta).src_index(0)
-    if n and times[0] <= t_first < ts._ts._t_end:
-        i_s = int(np.searchsorted(np.asarray(times), t_first, side="right")) - 1
-    r = []
-    for i in range(ta.size()):
-        p0, p1 = ta.period(i)
-        rv = float("nan")
-        if i_s is None:
-            if n and p0 <= times[0] < p1:
-                i_s = 0
-            else:
-                r.append(rv)
-                continue
-        if i_s < n and times[i_s] < p0:
-            i_s += 1
-        while i_s < n and times[i_s] < p1:
-            rv = fx(rv, float(vals[i_s]))
-            i_s += 1
-        r.append(rv)
-    return r
+def _percentile_plan(tsv, time_axis, host):
+    """The stored series and the views of a vector for region.ts_percentiles_csr: (row, t, v, t_end, fx, src, shift,
+    t0, dt, T). A shifted view that has not been read becomes (its source, its shift) and views of one source (by
+    object identity) share a row; the expressions still pending are evaluated together in one _ts_expr.evaluate call;
+    a concrete series is its own row with shift 0."""
+    pending = [ts for ts in tsv if ts._impl is None and ts._view_of is None]
+    if pending:
+        _ts_expr.evaluate(pending, host)
+    t0, dt, T = _api._resample_plan([], time_axis)[5:]
+    rows, row_of, src, shift, lo, hi = [], {}, [], [], [], []
+    for ts in tsv:
+        view = ts._impl is None
+        impl = ts._view_of if view else ts._impl
+        d = _api._to_us(ts._view_shift) if view else 0
+        if id(impl) not in row_of:
+            row_of[id(impl)] = len(rows)
+            rows.append(impl)
+            lo.append(t0 - d)
+            hi.append(t0 + T * dt - d)
+        r = row_of[id(impl)]
+        src.append(r)
+        shift.append(d)
+        lo[r], hi[r] = min(lo[r], t0 - d), max(hi[r], t0 + T * dt - d)
+    # a stored series is copied in the window its views read on this axis only (view_window, host/ts_percentiles.hpp)
+    return tuple(_api._percentile_rows(rows, lo, hi)) + (src, shift, t0, dt, T)
 
 
-def _nan_fold(pick):
-    """nan_min / nan_max (time_series_statistics.h:24-39): the fold ignores non-finite values."""
-    def fx(r, x):
-        if not np.isfinite(x):
-            return r
-        if not np.isfinite(r):
-            return x
-        return pick(r, x)
-    return fx
+def percentiles(ts_vector, time_axis, percentiles, *, host=True):
+    """api.percentiles (calculate_percentiles, time_series_statistics.h:184-246): every series goes through its true
+    average onto time_axis, non-finite samples are dropped, and each entry of `percentiles` (0..100 by R7,
+    statistics_property.AVERAGE, MIN_EXTREME / MAX_EXTREME) gives one series; the extremes are the true extremes of the
+    points inside each interval. The results carry the point interpretation of the first series.
 
-
-def percentiles(ts_vector, time_axis, percentiles):
-    """api.percentiles (calculate_percentiles, time_series_statistics.h:184-246), on the host: every series goes
-    through its true average onto time_axis, non-finite samples are dropped, and each entry of `percentiles` (0..100 by
-    R7, statistics_property.AVERAGE, MIN_EXTREME / MAX_EXTREME) gives one series; the extremes are the true extremes
-    of the points inside each interval. The results carry the point interpretation of the first series."""
-    from ..region import percentiles_host
+    host=True, the default, computes on the host (region.ts_percentiles_csr(host=True)). Unlike the newer batched
+    methods this function keeps the host as its default: it has callers and tests that run on machines without a
+    GPU, and its behaviour must not change for them. host=False is one fused device call, bit-identical; a vector of
+    more than region.TS_PERCENTILES_MAX_SERIES series or a list of more than region.PERCENTILES_MAX entries is
+    beyond the device's limits and goes to the host as well. The partitions of partition_by are passed as views of
+    their one stored series and are not materialised."""
+    from ..region import ts_percentiles_csr, TS_PERCENTILES_MAX_SERIES, PERCENTILES_MAX
     tsv, pcts = list(ts_vector), [int(p) for p in percentiles]
     fx_p = tsv[0].point_interpretation() if tsv else POINT_AVERAGE_VALUE
-    n = time_axis.size()
-    samples = np.empty((n, len(tsv)))
-    for k, ts in enumerate(tsv):
-        samples[:, k] = np.asarray(ts.average(time_axis)._ts._values)
-    values = percentiles_host(samples, pcts) if n and pcts else np.empty((len(pcts), n))
     out = TsVector()
-    for k, p in enumerate(pcts):
-        v = values[k]
-        if p in (statistics_property.MIN_EXTREME, statistics_property.MAX_EXTREME):
-            fx = _nan_fold(min if p == statistics_property.MIN_EXTREME else max)
-            v = [float("nan")] * n
-            for ts in tsv:  # extract_statistic_from_vector (:77-90)
-                v = [fx(a, b) for a, b in zip(v, _extract_statistics(ts, time_axis, fx))]
-        out.append(TimeSeries(time_axis, v, fx_p))
+    if not pcts:
+        return out
+    *csr, src, shift, t0, dt, T = _percentile_plan(tsv, time_axis, host)
+    on_host = host or len(tsv) > TS_PERCENTILES_MAX_SERIES or len(pcts) > PERCENTILES_MAX
+    values = ts_percentiles_csr(*csr, src, shift, t0, dt, T, pcts, host=on_host)
+    for k in range(len(pcts)):
+        out.append(TimeSeries(_impl=_api._PointTs(time_axis, values[k], fx_p)))
     return out
 
 
@@ -441,8 +544,9 @@ _percentiles_of = percentiles  # the method below has a parameter of the functio
 class TsVector(_Vector):
     """api.TsVector: a vector of TimeSeries (api_time_series.cpp)."""
 
-    def percentiles(self, time_axis, percentiles):
-        return _percentiles_of(self, time_axis, percentiles)
+    def percentiles(self, time_axis, percentiles, *, host=True):
+        """api.percentiles of this vector; host=True by default, as there"""
+        return _percentiles_of(self, time_axis, percentiles, host=host)
 
     def average(self, ta, *, host=False):
         """the true average of every series on a fixed_dt axis, all in one device call (region.resample), or with

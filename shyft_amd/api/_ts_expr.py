@@ -84,6 +84,9 @@ def evaluate(tsv, host=False):
     and run in one device call; with host=True, and for an expression beyond the device's stack depth or program
     length, on the host, bit-identical. Each result is cached in its TimeSeries."""
     from ..region import ts_expr_csr
+    for ts in tsv:
+        if ts._impl is None and ts._expr is None:
+            ts._ts  # a shifted view (TimeSeries.partition_by) becomes its concrete series
     todo = [ts for ts in tsv if ts._impl is None]
     if todo:
         terminals, prog_row, prog, consts, periods, orow, ot, fx, t_end, depth = _api._ts_expr_plan([ts._expr for ts in todo])

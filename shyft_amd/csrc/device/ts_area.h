@@ -1,6 +1,7 @@
 // accumulate_value on the device: the area of one point series over one period, statement by statement as
 // host/time_series.hpp accumulate_value (core/time_series.h:202-288). Shared by kernels/resample.hip (one period per
-// target interval) and kernels/tsprep.hip (one window per ice-packing query); there is one copy.
+// target interval), kernels/tsprep.hip (one window per ice-packing query) and kernels/ts_percentiles.hip (one period
+// per interval of a shifted view); there is one copy.
 //
 // Every operation is evaluated as written: int64 tick arithmetic, to_seconds(x) = double(x) / 1e6 as a division,
 // no FMA (-ffp-contract=off), isfinite by the exponent bits.
@@ -25,9 +26,19 @@ __device__ inline int64_t rs_min(int64_t a, int64_t b) { return a < b ? a : b; }
 
 // accumulate_value(source, [ps, pe), ., tsum, linear, strict_linear_between = true) over the n > 0 points t, v of
 // one series (host/time_series.hpp accumulate_value, statement by statement); tsum == 0 gives NaN
-__device__ inline double rs_area(const int64_t* __restrict__ t, const double* __restrict__ v, int64_t n, int64_t t_end,
-                                 int64_t ps, int64_t pe, bool linear, int64_t& tsum) {
+//
+// shift is added to every point time as it is read: the series seen `shift` later (time_shift_ts,
+// core/time_series_dd.h:707-751), t_end already moved by the caller. The linear branch takes to_seconds of absolute
+// times (rt, px_start + px_end), so moving the period instead would round differently; the stair-case branch uses
+// differences only. The default 0 is the series as stored.
+__device__ inline double rs_area(const int64_t* __restrict__ t_stored, const double* __restrict__ v, int64_t n,
+                                 int64_t t_end, int64_t ps, int64_t pe, bool linear, int64_t& tsum, int64_t shift = 0) {
     const bool extrapolate_flat = !linear;
+    const struct {
+        const int64_t* __restrict__ p;
+        int64_t d;
+        __device__ int64_t operator[](int64_t k) const { return p[k] + d; }
+    } t{t_stored, shift};
     tsum = 0;
     // open_range_index_of(ps): -1 before the first point, n - 1 from the last point on
     int64_t i;

@@ -22,6 +22,7 @@
 #include "qm.hpp"
 #include "region_model.hpp"
 #include "ts_expr.hpp"
+#include "ts_percentiles.hpp"
 
 namespace py = pybind11;
 using namespace shyft_hip::host;
@@ -52,6 +53,36 @@ py::tuple series_csr(const py::list& series) {
     for (size_t s = 0; s < S; ++s) {
         std::copy(src[s]->t.begin(), src[s]->t.end(), t.mutable_data() + r[s]);
         std::copy(src[s]->v.begin(), src[s]->v.end(), v.mutable_data() + r[s]);
+    }
+    return py::make_tuple(row, t, v, t_end, fx);
+}
+
+// The same for api.percentiles: row s keeps the points that its views can read on an axis (view_window of
+// host/ts_percentiles.hpp), lo[s] and hi[s] the axis' start and end taken back by the largest and the smallest shift of
+// the views of row s
+py::tuple percentile_rows(const py::list& series, const std::vector<int64_t>& lo, const std::vector<int64_t>& hi) {
+    std::vector<const point_ts*> src;
+    for (auto h : series) src.push_back(&h.cast<const point_ts&>());
+    const size_t S = src.size();
+    if (lo.size() != S || hi.size() != S) throw std::runtime_error("percentiles: one window per stored series");
+    const py::ssize_t n_series = py::ssize_t(S);
+    py::array_t<int64_t> row(n_series + 1), t_end(n_series);
+    py::array_t<int32_t> fx(n_series);
+    std::vector<std::pair<size_t, size_t>> keep(S);
+    int64_t* r = row.mutable_data();
+    r[0] = 0;
+    for (size_t s = 0; s < S; ++s) {
+        keep[s] = view_window(*src[s], lo[s], hi[s]);
+        r[s + 1] = r[s] + int64_t(keep[s].second - keep[s].first);
+        t_end.mutable_data()[s] = src[s]->t_end;
+        fx.mutable_data()[s] = int32_t(src[s]->fx);
+    }
+    const py::ssize_t n_points = py::ssize_t(r[S]);
+    py::array_t<int64_t> t(n_points);
+    py::array_t<double> v(n_points);
+    for (size_t s = 0; s < S; ++s) {
+        std::copy(src[s]->t.begin() + keep[s].first, src[s]->t.begin() + keep[s].second, t.mutable_data() + r[s]);
+        std::copy(src[s]->v.begin() + keep[s].first, src[s]->v.begin() + keep[s].second, v.mutable_data() + r[s]);
     }
     return py::make_tuple(row, t, v, t_end, fx);
 }
@@ -341,6 +372,8 @@ PYBIND11_MODULE(_api, m) {
         .def("point_interpretation", [](const point_ts& s) { return s.fx; })
         .def("total_period", [](const point_ts& s) { auto p = s.total_period(); return std::make_pair(to_s(p.start), to_s(p.end)); })
         .def("__call__", [](const point_ts& s, double t) { return s(to_us(t)); })
+        // the interval that holds t, -1 outside the series (point_ts::index_of, core/time_series.h:343)
+        .def("index_of", [](const point_ts& s, double t) { auto i = index_of(s, to_us(t)); return i == npos ? int64_t(-1) : int64_t(i); })
         .def_property_readonly("_values", [](const point_ts& s) { return py::array_t<double>(s.v.size(), s.v.data()); })
         .def_property_readonly("_times", [](const point_ts& s) {
             std::vector<double> t(s.t.size());
@@ -717,6 +750,7 @@ PYBIND11_MODULE(_api, m) {
     });
     // The host work of region.forecast_skill_csr callers: the CSR arrays alone, and seconds as ticks.
     m.def("_series_csr", &series_csr);
+    m.def("_percentile_rows", &percentile_rows);
     m.def("_to_us", &to_us);
     m.def("_ts_expr_plan", &ts_expr_plan);
     // TsVector.forecast_merge (host/forecast.hpp; core/time_series_merge.h:47-99)

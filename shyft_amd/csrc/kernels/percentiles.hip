@@ -30,6 +30,7 @@
 #include <stdint.h>
 #include <vector>
 
+#include "../device/pct_plan.h"
 #include "../include_internal/kernels.h"
 
 namespace {
@@ -38,66 +39,8 @@ constexpr int PB = 256;                 // 4 wavefronts
 constexpr int PCT_MAX = SHYFT_HIP_PERCENTILES_MAX;
 constexpr int PCT_SEL = 2 * PCT_MAX;    // selections (ranks) per job: lower and upper of every percentile
 constexpr int PCT_CHUNK = 16384;        // cells of a job's row per histogram workgroup
-constexpr uint64_t SIGN = 0x8000000000000000ull;
-constexpr uint64_t EXPO = 0x7ff0000000000000ull;
 
-enum { PCT_NAN = 0, PCT_SINGLE = 1, PCT_LERP = 2, PCT_AVG = 3 };
-struct pct_plan {
-    int kind;
-    uint32_t lo, hi;
-    double delta;
-};
-
-// What percentile p of ns sorted samples reads (time_series_statistics.h:119-157; R7 with the eps rules), and the
-// extremes on the model's own axis (nan_min / nan_max of one value per series, :25-39, :77-90, :221-226).
-__host__ __device__ inline pct_plan pct_make_plan(int64_t p, int ns) {
-    pct_plan r{PCT_NAN, 0u, 0u, 0.0};
-    if (ns <= 0) return r;
-    if (p == -1) {
-        r.kind = PCT_AVG;
-    } else if (p == -1000) {
-        r.kind = PCT_SINGLE;
-    } else if (p == 1000) {
-        r.kind = PCT_SINGLE;
-        r.lo = uint32_t(ns - 1);
-    } else if (p >= 0 && p <= 100) {
-        const double eps = 1e-30;
-        double nd = 1.0 + (ns - 1) * double(p) / 100.0;
-        int n = int(nd);
-        double delta = nd - n;
-        --n;
-        r.kind = PCT_SINGLE;
-        if (n <= 0 && delta <= eps) {
-            r.lo = 0u;
-        } else if (n >= ns) {
-            r.lo = uint32_t(ns - 1);
-        } else if (delta < eps) {
-            r.lo = uint32_t(n);
-        } else {
-            r.kind = PCT_LERP;
-            r.lo = uint32_t(n);
-            r.hi = uint32_t(n < ns - 1 ? n + 1 : n);
-            r.delta = delta;
-        }
-    }
-    return r;
-}
-
-__device__ inline bool key_of(double v, uint64_t& key) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    key = (u & SIGN) ? ~u : (u | SIGN);
-    return (u & EXPO) != EXPO;  // finite
-}
-__device__ inline double value_of(uint64_t key) {
-    const uint64_t u = (key & SIGN) ? (key ^ SIGN) : ~key;
-    return __longlong_as_double((long long)u);
-}
-__device__ inline double pct_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-__device__ inline double pct_value(const pct_plan& pl, double lower, double upper) {
-    if (pl.kind == PCT_SINGLE) return lower;
-    return lower + pl.delta * (upper - lower);  // separately rounded multiply and add (-ffp-contract=off)
-}
+// pct_plan / pct_make_plan, key_of / value_of and pct_value: device/pct_plan.h, shared with kernels/ts_percentiles.hip
 
 // ---------------------------------------------------------------------------------------------- AVERAGE
 __device__ inline double wave_sum(double v) {

@@ -613,6 +613,65 @@ def resample_last_path(device: int = -1) -> int:
     return int(lib().shyft_hip_resample_last_path(device))
 
 
+# ---- percentiles of a vector of series on a fixed_dt axis (kernels/ts_percentiles.hip) ---------------------------------
+TS_PERCENTILES_MAX_SERIES = 4096
+TS_PERCENTILES_PATH_AUTO, TS_PERCENTILES_PATH_WAVE, TS_PERCENTILES_PATH_LDS = 0, 1, 2
+
+
+def ts_percentiles_csr(row, t, v, t_end, fx, src, shift, ta_t0: int, ta_dt: int, T: int, pcts, device: int = -1,
+                       host: bool = False) -> np.ndarray:
+    """Percentiles across S views of R stored series on a fixed_dt axis in one fused device call
+    (shyft_hip_ts_percentiles; calculate_percentiles, core/time_series_statistics.h:184-246). The stored series are in
+    the CSR form of resample_csr; view s is series src[s] moved shift[s] microseconds later, so many views can share one
+    stored series. Each entry of pcts is 0..100 (R7), STAT_AVERAGE, or STAT_MIN_EXTREME / STAT_MAX_EXTREME (the
+    extremes of the points inside each interval). On the device S is at most TS_PERCENTILES_MAX_SERIES and len(pcts)
+    at most PERCENTILES_MAX. host=True evaluates the same values with the host restatement
+    (shyft_hip_ts_percentiles_host, no limits), which the device result is bit-identical to. Returns [len(pcts)][T]; a
+    call without views gives NaN."""
+    R, row, t, v, t_end, fx = _csr_series("ts_percentiles", row, t, v, t_end, fx)
+    src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+    shift = np.ascontiguousarray(shift, dtype=np.int64).reshape(-1)
+    if src.shape[0] != shift.shape[0]:
+        raise ValueError("ts_percentiles: src and shift must have one entry per view")
+    p = np.ascontiguousarray(list(pcts), dtype=np.int64).reshape(-1)
+    out = np.full((p.size, int(T)), np.nan, dtype=np.float64)
+    fn = lib().shyft_hip_ts_percentiles_host if host else lib().shyft_hip_ts_percentiles
+    check(fn(device, R, _ptr(row), _ptr(t), _ptr(v), _ptr(t_end), _ptr(fx), src.shape[0], _ptr(src), _ptr(shift),
+             int(ta_t0), int(ta_dt), int(T), _ptr(p), p.size, _ptr(out)), None)
+    return out
+
+
+def ts_percentiles(series, time_axis, pcts, device: int = -1, host: bool = False) -> np.ndarray:
+    """ts_percentiles_csr over a list of the api's `_PointTs`, each its own stored series, on a TimeAxisFixedDeltaT.
+    Returns [len(pcts)][T]."""
+    from .api import _api
+    row, t, v, t_end, fx, t0, dt, T = _api._resample_plan(list(series), time_axis)
+    S = len(t_end)
+    return ts_percentiles_csr(row, t, v, t_end, fx, np.arange(S), np.zeros(S, np.int64), t0, dt, T, pcts, device=device,
+                              host=host)
+
+
+def ts_percentiles_last_ms(device: int = -1) -> float:
+    """HIP-event milliseconds of the kernel of the last ts_percentiles on the device, copies excluded."""
+    return float(lib().shyft_hip_ts_percentiles_last_ms(device))
+
+
+def ts_percentiles_calls(device: int = -1) -> int:
+    """The number of ts_percentiles calls that launched on the device so far."""
+    return int(lib().shyft_hip_ts_percentiles_calls(device))
+
+
+def ts_percentiles_set_path(path: int) -> None:
+    """TS_PERCENTILES_PATH_WAVE or TS_PERCENTILES_PATH_LDS forces the launch shape of ts_percentiles for the process,
+    TS_PERCENTILES_PATH_AUTO gives the choice back (test and measurement aid)."""
+    check(lib().shyft_hip_ts_percentiles_set_path(int(path)), None)
+
+
+def ts_percentiles_last_path(device: int = -1) -> int:
+    """TS_PERCENTILES_PATH_WAVE or TS_PERCENTILES_PATH_LDS: the launch shape of the last ts_percentiles on the device."""
+    return int(lib().shyft_hip_ts_percentiles_last_path(device))
+
+
 # ---- observation preparation: rating curve, ice packing, recession, min-max fill (kernels/tsprep.hip) ------------------
 ICE_DISALLOW_MISSING, ICE_ALLOW_INITIAL_MISSING, ICE_ALLOW_ANY_MISSING = 0, 1, 2
 
