@@ -851,6 +851,8 @@ int shyft_hip_math_selftest(int fn, const double* x, const double* y, size_t n, 
  * fn, a column count that is not the function's, a null array or a HIP error.
  *   fn                                in columns                  out columns
  *   EXPLOG_INLINE  (pt_gs_k)          x                           exp_fast(x), log_fast(x)
+ *   EXPLOG_PAIRS   (pt_gs_k)          x, y                        the step loop's inline pairs: exp2(x, y).a, .b,
+ *                                                                 log2p(x, y).a, .b (device/pt_dev.h kmath<true>)
  *   EXPLOG_CALLS   (pt_gs_k)          x, y                        dexp(x), dlog(x), dexp2(x, y).a, .b
  *   EXPLOG_TABLE   (pt_ss_k)          x, y                        the same functions as built there
  *   POWERS         (pt_gs_k)          x, y                        dpowr(x, y), dpow4(x), dpow8(x), dpow(x, y)
@@ -877,6 +879,7 @@ int shyft_hip_math_selftest(int fn, const double* x, const double* y, size_t n, 
 #define SHYFT_HIP_DST_SKAUGEN_GROUP4 10
 #define SHYFT_HIP_DST_BRENT_OPEN4 11
 #define SHYFT_HIP_DST_BRENT_OPEN2 12
+#define SHYFT_HIP_DST_EXPLOG_PAIRS 13
 int shyft_hip_device_selftest(int fn, const double* in, size_t n_in_cols, size_t n, double* out, size_t n_out_cols);
 
 #ifdef __cplusplus

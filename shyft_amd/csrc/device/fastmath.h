@@ -54,6 +54,31 @@ __device__ __forceinline__ double gsb_exp(double x, const gsb_k& k) {
     return __builtin_ldexp(__builtin_fma(r, q, 1.0), (int)kf);
 }
 
+// two values of one elementary function (dexp2 of device/special.h, kmath's exp2 / log2p of device/pt_dev.h)
+struct dexp_pair {
+    double a, b;
+};
+
+// gsb_exp of two independent arguments, step by step side by side: one basic block, so each chain's fma latency
+// is hidden behind the other's -- the same instructions and the same bits as gsb_exp(x), gsb_exp(y)
+__device__ __forceinline__ dexp_pair gsb_exp2(double x, double y, const gsb_k& k) {
+    const double tx = gs_fma_s(x, k.c[0], k.c[1]), ty = gs_fma_s(y, k.c[0], k.c[1]);
+    const double kx = tx - k.c[1], ky = ty - k.c[1];
+    double rx = __builtin_fma(-kx, k.c[2], x), ry = __builtin_fma(-ky, k.c[2], y);
+    rx = __builtin_fma(-kx, k.c[3], rx);
+    ry = __builtin_fma(-ky, k.c[3], ry);
+    double qx = gs_fma_s(rx, k.c[4], k.c[5]), qy = gs_fma_s(ry, k.c[4], k.c[5]);
+#pragma unroll
+    for (int i = 6; i <= 14; ++i) {
+        qx = gs_fma_s(qx, rx, k.c[i]);
+        qy = gs_fma_s(qy, ry, k.c[i]);
+    }
+    dexp_pair r;
+    r.a = __builtin_ldexp(__builtin_fma(rx, qx, 1.0), (int)kx);
+    r.b = __builtin_ldexp(__builtin_fma(ry, qy, 1.0), (int)ky);
+    return r;
+}
+
 // detmath::log for positive normal finite x (detmath::log_core with k_adj = 0, step by step)
 __device__ __forceinline__ double gsb_log(double x, const gsb_k& k) {
     uint64_t u = (uint64_t)__double_as_longlong(x);
@@ -75,6 +100,47 @@ __device__ __forceinline__ double gsb_log(double x, const gsb_k& k) {
         return dk * k.c[2] - ((hfsq - __builtin_fma(s, hfsq + R, dk * k.c[3])) - f);
     }
     return dk * k.c[2] - (__builtin_fma(s, f - R, -(dk * k.c[3])) - f);
+}
+
+// gsb_log of two independent arguments, step by step side by side as gsb_exp2 -- the same instructions and the
+// same bits as gsb_log(x), gsb_log(y)
+__device__ __forceinline__ dexp_pair gsb_log2(double x, double y, const gsb_k& k) {
+    uint64_t ux = (uint64_t)__double_as_longlong(x), uy = (uint64_t)__double_as_longlong(y);
+    int ex = (int)((ux >> 52) & 0x7ff) - 1023, ey = (int)((uy >> 52) & 0x7ff) - 1023;
+    const uint32_t hx = (uint32_t)(ux >> 32) & 0x000fffffu, hy = (uint32_t)(uy >> 32) & 0x000fffffu;
+    const uint32_t ix = (hx + 0x95f64u) & 0x100000u, iy = (hy + 0x95f64u) & 0x100000u;
+    ux = (ux & 0x000fffffffffffffull) | ((uint64_t)(ix ^ 0x3ff00000u) << 32);
+    uy = (uy & 0x000fffffffffffffull) | ((uint64_t)(iy ^ 0x3ff00000u) << 32);
+    ex += (int)(ix >> 20);
+    ey += (int)(iy >> 20);
+    const double fx = __longlong_as_double((long long)ux) - 1.0, fy = __longlong_as_double((long long)uy) - 1.0;
+    const double sx = fx / (2.0 + fx), sy = fy / (2.0 + fy);
+    const double dkx = (double)ex, dky = (double)ey;
+    const double zx = sx * sx, zy = sy * sy;
+    const double wx = zx * zx, wy = zy * zy;
+    double ax = gs_fma_s(wx, k.c[20], k.c[18]), ay = gs_fma_s(wy, k.c[20], k.c[18]);
+    double bx = gs_fma_s(wx, k.c[21], k.c[19]), by = gs_fma_s(wy, k.c[21], k.c[19]);
+    ax = gs_fma_s(wx, ax, k.c[16]);
+    ay = gs_fma_s(wy, ay, k.c[16]);
+    bx = gs_fma_s(wx, bx, k.c[17]);
+    by = gs_fma_s(wy, by, k.c[17]);
+    bx = gs_fma_s(wx, bx, k.c[15]);
+    by = gs_fma_s(wy, by, k.c[15]);
+    const double Rx = zx * bx + wx * ax, Ry = zy * by + wy * ay;
+    dexp_pair r;
+    if (((int32_t)(hx - 0x6147au) | (int32_t)(0x6b851u - hx)) > 0) {
+        const double hfsq = 0.5 * fx * fx;
+        r.a = dkx * k.c[2] - ((hfsq - __builtin_fma(sx, hfsq + Rx, dkx * k.c[3])) - fx);
+    } else {
+        r.a = dkx * k.c[2] - (__builtin_fma(sx, fx - Rx, -(dkx * k.c[3])) - fx);
+    }
+    if (((int32_t)(hy - 0x6147au) | (int32_t)(0x6b851u - hy)) > 0) {
+        const double hfsq = 0.5 * fy * fy;
+        r.b = dky * k.c[2] - ((hfsq - __builtin_fma(sy, hfsq + Ry, dky * k.c[3])) - fy);
+    } else {
+        r.b = dky * k.c[2] - (__builtin_fma(sy, fy - Ry, -(dky * k.c[3])) - fy);
+    }
+    return r;
 }
 
 }  // namespace shyft_dev

@@ -22,6 +22,12 @@ struct kmath {
     __device__ double exp(double x) const { return dexp(x); }
     __device__ double log(double x) const { return dlog(x); }
     __device__ dexp_pair exp2(double x, double y) const { return dexp2(x, y); }
+    __device__ dexp_pair log2p(double x, double y) const {
+        dexp_pair r;
+        r.a = dlog(x);
+        r.b = dlog(y);
+        return r;
+    }
 };
 // every call loads its own constants (one scalar-cache read per call): short SGPR live ranges instead of 54 SGPRs
 // held across the caller (r05, pt_gs_k: v_readlane 270 -> 224 in the kernel's code, 78.85 -> 78.45 ms per chunk)
@@ -30,11 +36,29 @@ struct kmath<true> {
     __device__ kmath() {}
     __device__ double exp(double x) const { return exp_fast(x, gsb_load()); }
     __device__ double log(double x) const { return log_fast(x, gsb_load()); }
+    // two independent exps: both fast-path bodies side by side in one basic block (gsb_exp2), then ONE test for the
+    // general path, inside which each argument beyond the domain takes the call as exp_fast does. (Two exp_fast in
+    // a row each end in their own branch, which keeps the second polynomial behind the first.) The same bits.
     __device__ dexp_pair exp2(double x, double y) const {
-        const gsb_k k = gsb_load();
-        dexp_pair r;
-        r.a = exp_fast(x, k);
-        r.b = exp_fast(y, k);
+        dexp_pair r = gsb_exp2(x, y, gsb_load());
+        if (!(__builtin_fabs(x) <= 708.0 && __builtin_fabs(y) <= 708.0)) {
+            if (!(__builtin_fabs(x) <= 708.0)) r.a = dexp(x);
+            if (!(__builtin_fabs(y) <= 708.0)) r.b = dexp(y);
+        }
+        return r;
+    }
+    // two independent logs, the same way: gsb_log2, one merged domain test, dlog per argument beyond it. No step
+    // calls it yet: Priestley-Taylor's log beside Kirchner's opening log(q) measured inside the run-to-run spread
+    // in pt_gs_k and was left out; the pair is kept, with its device test (EXPLOG_PAIRS), for the
+    // next place that has two independent logs.
+    __device__ dexp_pair log2p(double x, double y) const {
+        dexp_pair r = gsb_log2(x, y, gsb_load());
+        const bool fx = x >= 2.2250738585072014e-308 && x <= 1.7976931348623157e308;
+        const bool fy = y >= 2.2250738585072014e-308 && y <= 1.7976931348623157e308;
+        if (!(fx && fy)) {
+            if (!fx) r.a = dlog(x);
+            if (!fy) r.b = dlog(y);
+        }
         return r;
     }
 };
@@ -59,8 +83,9 @@ __device__ inline double pt_pot_evap(double albedo, double alpha, double tempera
     return epot / (2500780 - 2361 * temperature);
 }
 
-// the same, plus exp(ae_arg) for the caller's actual_evapotranspiration (inline beside the saturation
-// pressure's exp (two independent exps side by side instead of back to back); the same bits as the two calls
+// the same, plus exp(ae_arg) for the caller's actual_evapotranspiration, beside the saturation pressure's exp: one
+// dexp2 call (INL = false), or kmath<true>::exp2's two inline bodies in one basic block with one merged
+// general-path test (INL = true); the same bits as the two calls
 template <bool INL = false>
 __device__ inline double pt_pot_evap_exp(double albedo, double alpha, double temperature, double global_radiation,
                                          double rhumidity, double ae_arg, double& ae_exp) {

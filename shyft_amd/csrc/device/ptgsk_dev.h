@@ -495,7 +495,9 @@ __device__ inline double kirchner_f(double ln_q, double p_minus_e, double c1, do
 // Returns false if a do_step needed 500 attempts (odeint failed_step_checker).
 // INL: the step's exps and logs inline by the gamma_lean.h fast paths (one SGPR constant table per call, the general
 // out-of-line functions only beyond them) instead of out-of-line dexp2 / dexp / dlog calls -- the same bits (pt_gs_k:
-// 90.8 -> 89.7 ms per 730-step chunk; the other stacks keep the calls, device/pt_dev.h)
+// 90.8 -> 89.7 ms per 730-step chunk; the other stacks keep the calls, device/pt_dev.h). kirchner_f's two exps go
+// through kmath::exp2: inline, that is both polynomial chains interleaved in one basic block and one merged test
+// for the general path (device/pt_dev.h), as dexp2 interleaves them out of line.
 template <bool INL = false>
 __device__ inline bool kirchner_step(double& q, double& q_avg, double p, double e, double t1, double c1, double c2,
                                      double c3) {

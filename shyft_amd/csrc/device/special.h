@@ -43,10 +43,10 @@ __device__ __noinline__ double dexp(double x) { return detmath::exp(x); }
 __device__ __noinline__ double dlog(double x) { return detmath::log(x); }
 #endif
 // two exps in one out-of-line call: the two Horner chains interleave (each one's fma latency hidden behind the
-// other's), where two calls would run them back to back; the same bits as two dexp calls
-struct dexp_pair {
-    double a, b;
-};
+// other's), where two calls would run them back to back; the same bits as two dexp calls (dexp_pair:
+// device/fastmath.h). This is the out-of-line pair; the step loops that take their mathematics inline get the same
+// interleave from kmath<true>::exp2 (device/pt_dev.h: gsb_exp2 and one merged general-path test -- two exp_fast
+// in a row do NOT interleave, each ends in its own branch)
 __device__ __noinline__ dexp_pair dexp2(double x, double y) {
     dexp_pair r;
 #if SHYFT_TABLE_CALLS

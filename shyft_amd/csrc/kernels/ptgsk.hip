@@ -451,7 +451,8 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
         double gm_melt_m3s = 0.0;
         if (!(glacier_area_m2 <= sca_area || temp <= 0.0))
             gm_melt_m3s = dtf * temp * (glacier_area_m2 - sca_area) * (0.001 / 86400.0);
-        // Priestley-Taylor's saturation-pressure exp and actual_evapotranspiration's exp in one dexp2 call
+        // Priestley-Taylor's saturation-pressure exp beside actual_evapotranspiration's exp: kmath<true>::exp2, both
+        // inline bodies interleaved in one basic block (device/pt_dev.h)
         double ae_exp;
         const double pot_evap =
             pt_pot_evap_exp<true>(P[PK_PT_ALBEDO], P[PK_PT_ALPHA], temp, rad, rel_hum, -q * 3.0 / P[PK_AE_SCALE], ae_exp) *
@@ -560,6 +561,22 @@ __global__ __launch_bounds__(ST_BLOCK, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_st_e
     const double x = in[i];
     out[i] = km.exp(x);
     out[n + i] = km.log(x);
+}
+
+// the step loop's two-argument inline exp and log (kmath<true>::exp2 / log2p: both fast paths side by side, one
+// merged test for the general path)
+__global__ __launch_bounds__(ST_BLOCK, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_st_explog_pairs_kernel(
+    const double* __restrict__ in, size_t n, double* __restrict__ out) {
+    const size_t i = blockIdx.x * (size_t)ST_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const kmath<true> km;
+    const double x = in[i], y = in[n + i];
+    const dexp_pair e = km.exp2(x, y);
+    const dexp_pair l = km.log2p(x, y);
+    out[i] = e.a;
+    out[n + i] = e.b;
+    out[2 * n + i] = l.a;
+    out[3 * n + i] = l.b;
 }
 
 __global__ __launch_bounds__(ST_BLOCK, SHYFT_PTGSK_BUDGET_WAVES) void ptgsk_st_explog_calls_kernel(
@@ -736,6 +753,7 @@ hipError_t launch_ptgsk_selftest(int fn, const double* in, size_t n, double* out
     switch (fn) {
         case SHYFT_HIP_DST_EXPLOG_INLINE: hipLaunchKernelGGL(ptgsk_st_explog_inline_kernel, grid, block, 0, stream, in, n, out); break;
         case SHYFT_HIP_DST_EXPLOG_CALLS: hipLaunchKernelGGL(ptgsk_st_explog_calls_kernel, grid, block, 0, stream, in, n, out); break;
+        case SHYFT_HIP_DST_EXPLOG_PAIRS: hipLaunchKernelGGL(ptgsk_st_explog_pairs_kernel, grid, block, 0, stream, in, n, out); break;
         case SHYFT_HIP_DST_POWERS: hipLaunchKernelGGL(ptgsk_st_powers_kernel, grid, block, 0, stream, in, n, out); break;
         case SHYFT_HIP_DST_GAMMA_LEAN: hipLaunchKernelGGL(ptgsk_st_gamma_kernel, grid, block, 0, stream, in, n, out); break;
         case SHYFT_HIP_DST_BRENT: hipLaunchKernelGGL(ptgsk_st_brent_kernel, grid, block, 0, stream, in, n, out); break;

@@ -55,7 +55,8 @@ extern "C" int shyft_hip_device_selftest(int fn, const double* in, size_t n_in_c
     // in / out columns of each function code, and the kernel file that serves it
     static const struct { size_t n_in, n_out; bool ptssk; } spec[] = {
         {1, 2, false}, {2, 4, false}, {2, 4, true}, {2, 4, false}, {2, 4, false}, {6, 2, false},
-        {6, 1, false}, {6, 1, false}, {4, 2, true}, {4, 2, true}, {4, 2, true}, {6, 1, false}, {6, 1, false}};
+        {6, 1, false}, {6, 1, false}, {4, 2, true}, {4, 2, true}, {4, 2, true}, {6, 1, false}, {6, 1, false},
+        {2, 4, false}};
     if (fn < 0 || fn >= (int)(sizeof spec / sizeof spec[0]) || !in || !out) return 1;
     if (n_in_cols != spec[fn].n_in || n_out_cols != spec[fn].n_out) return 1;
     if (n == 0) return 0;
