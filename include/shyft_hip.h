@@ -206,6 +206,11 @@ int shyft_hip_interpolate_btk(shyft_hip_region* h, size_t n_sources, const doubl
 int shyft_hip_btk(int device, size_t n_sources, const double* src_xyz, const double* src_values, size_t n,
                   const double* prior_gradient, const double* btk_param, size_t n_dst, const double* dst_xyz,
                   double* out);
+/* shyft_hip_btk with at most block_steps steps of one valid-source pattern per product and placement (0 = the
+ * default, bounded by memory only): a test aid that makes a short series take the multi-block path. */
+int shyft_hip_btk_blocked(int device, size_t n_sources, const double* src_xyz, const double* src_values, size_t n,
+                          const double* prior_gradient, const double* btk_param, size_t n_dst, const double* dst_xyz,
+                          double* out, size_t block_steps);
 
 /* Stateless ordinary kriging (api/boostpython/api_interpolation.cpp:86-148; covariances and the system of
  * core/kriging.h:23-135) on a device (device < 0 = current): weights = first n_sources rows of A^-1 B, A^-1 by LU

@@ -51,6 +51,8 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p]),
     "shyft_hip_btk": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p, C.c_void_p]),
+    "shyft_hip_btk_blocked": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
     "shyft_hip_ordinary_kriging": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                              C.c_size_t, C.c_void_p, C.c_void_p]),
     "shyft_hip_ordinary_kriging_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,

@@ -251,6 +251,7 @@ struct btk_args {
     const int32_t* d_dst_index;    // device [D] output column of each destination, or null (= d)
     double* d_out;                 // device: step j, destination d -> d_out[j * ld_out + column]
     size_t ld_out;
+    size_t max_block_steps;        // cap on the steps of one pattern per product and placement, 0 = by memory only
 };
 void btk_run(const btk_args& a, hipStream_t stream);
 

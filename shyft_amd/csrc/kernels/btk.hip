@@ -63,17 +63,26 @@ struct devbuf {
     }
 };
 
-rocblas_handle blas_handle(int device) {
+// One rocBLAS handle per device, with the mutex that makes it unshareable: a handle carries ONE stream
+// (rocblas_set_stream) and is not usable from two threads at once, and shards of one region on one device, or two
+// regions driven from two threads, reach btk_run concurrently. btk_run holds `use` from rocblas_set_stream until
+// its last synchronise, so every product of a call is issued on, and ordered within, that call's stream. Calls on
+// distinct devices hold distinct mutexes and still run side by side.
+struct device_blas {
+    rocblas_handle handle = nullptr;
+    std::mutex use;
+};
+device_blas& blas_of(int device) {
     static std::mutex mu;
-    static std::map<int, rocblas_handle> handles;
+    static std::map<int, device_blas> per_device;  // node-based: references stay valid
     std::lock_guard<std::mutex> lock(mu);
-    auto f = handles.find(device);
-    if (f != handles.end()) return f->second;
-    rocblas_handle h = nullptr;
-    check(rocblas_create_handle(&h), "rocblas_create_handle");
-    handles[device] = h;
-    return h;
+    device_blas& b = per_device[device];
+    if (!b.handle) check(rocblas_create_handle(&b.handle), "rocblas_create_handle");
+    return b;
 }
+
+// steps per scatter launch: gridDim.y of btk_scatter_kernel, kept at the portable limit
+constexpr size_t SCATTER_MAX_ROWS = 65535;
 
 // ---- device kernels ---------------------------------------------------------------------------------------------
 // k[j][d] = (sill - nug) exp(-zscaled_distance(src_j, dst_d) / range)  (utils::cov, bayesian_kriging.h:53-56)
@@ -246,14 +255,27 @@ struct btk_cache {
 btk_cache* btk_cache_create() { return new btk_cache(); }
 void btk_cache_destroy(btk_cache* c) { delete c; }
 
+static void btk_run_on(rocblas_handle blas, const btk_args& a, hipStream_t stream);
+
 void btk_run(const btk_args& a, hipStream_t stream) {
-    const size_t S = a.n_sources, D = a.n_dst, T = a.n_steps;
-    if (S == 0 || D == 0 || T == 0) return;
-    if (D > size_t(INT32_MAX) || S > 4096) throw std::runtime_error("btk: too many sources or destinations");
+    if (a.n_sources == 0 || a.n_dst == 0 || a.n_steps == 0) return;
+    if (a.n_dst > size_t(INT32_MAX) || a.n_sources > 4096)
+        throw std::runtime_error("btk: too many sources or destinations");
     int device = 0;
     check(hipGetDevice(&device), "hipGetDevice");
-    rocblas_handle blas = blas_handle(device);
-    check(rocblas_set_stream(blas, stream), "rocblas_set_stream");
+    device_blas& b = blas_of(device);
+    std::lock_guard<std::mutex> only(b.use);  // until the last synchronise below (see device_blas)
+    check(rocblas_set_stream(b.handle, stream), "rocblas_set_stream");
+    try {
+        btk_run_on(b.handle, a, stream);
+    } catch (...) {
+        (void)hipStreamSynchronize(stream);  // products issued before the error leave the handle before the next call
+        throw;
+    }
+}
+
+static void btk_run_on(rocblas_handle blas, const btk_args& a, hipStream_t stream) {
+    const size_t S = a.n_sources, D = a.n_dst, T = a.n_steps;
     const double c0 = a.sill - a.nug, inv_sd2 = 1 / (a.gradient_sd * a.gradient_sd);
 
     // valid-source patterns in order of first appearance; an all-invalid step is the reference's error
@@ -295,7 +317,8 @@ void btk_run(const btk_args& a, hipStream_t stream) {
     const double one = 1.0, zero = 0.0;
     devbuf<double> d_src, d_zsrc, d_k, d_A, d_kinv, d_tobs, d_C;
     devbuf<int32_t> d_steps;
-    const size_t block_steps = std::max<size_t>(1, std::min<size_t>(T, (size_t(1) << 29) / D));  // temp <= 4 GiB
+    size_t block_steps = std::max<size_t>(1, std::min<size_t>(T, (size_t(1) << 29) / D));  // temp <= 4 GiB
+    if (a.max_block_steps) block_steps = std::min(block_steps, a.max_block_steps);
     for (size_t p = 0; p < patterns.size(); ++p) {
         std::vector<size_t> idx;
         for (size_t s = 0; s < S; ++s)
@@ -367,9 +390,13 @@ void btk_run(const btk_args& a, hipStream_t stream) {
                 std::vector<int32_t> st(nb);
                 for (size_t j = 0; j < nb; ++j) st[j] = int32_t(steps[b0 + j]);
                 d_steps.upload(st.data(), nb, stream);
-                hipLaunchKernelGGL(btk_scatter_kernel, dim3(unsigned((D + 255) / 256), unsigned(nb)), dim3(256), 0,
-                                   stream, d_C.p, int(D), int(nb), d_steps.p, a.d_dst_index, a.d_out, a.ld_out);
-                check(hipGetLastError(), "scatter kernel");
+                for (size_t j0 = 0; j0 < nb; j0 += SCATTER_MAX_ROWS) {
+                    const size_t rows = std::min(SCATTER_MAX_ROWS, nb - j0);
+                    hipLaunchKernelGGL(btk_scatter_kernel, dim3(unsigned((D + 255) / 256), unsigned(rows)), dim3(256),
+                                       0, stream, d_C.p + j0 * D, int(D), int(rows), d_steps.p + j0, a.d_dst_index,
+                                       a.d_out, a.ld_out);
+                    check(hipGetLastError(), "scatter kernel");
+                }
             }
             check(hipStreamSynchronize(stream), "sync");  // host buffers of this block are reused
         }

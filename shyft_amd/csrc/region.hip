@@ -999,6 +999,13 @@ int shyft_hip_interpolate_btk(shyft_hip_region* h, size_t n_sources, const doubl
 int shyft_hip_btk(int device, size_t n_sources, const double* src_xyz, const double* src_values, size_t n,
                   const double* prior_gradient, const double* btk_param, size_t n_dst, const double* dst_xyz,
                   double* out) {
+    return shyft_hip_btk_blocked(device, n_sources, src_xyz, src_values, n, prior_gradient, btk_param, n_dst, dst_xyz,
+                                 out, 0);
+}
+
+int shyft_hip_btk_blocked(int device, size_t n_sources, const double* src_xyz, const double* src_values, size_t n,
+                          const double* prior_gradient, const double* btk_param, size_t n_dst, const double* dst_xyz,
+                          double* out, size_t block_steps) {
     if (!src_xyz || !src_values || !prior_gradient || !btk_param || !dst_xyz || !out)
         return fail(nullptr, "shyft_hip_btk: null argument");
     try {
@@ -1030,6 +1037,7 @@ int shyft_hip_btk(int device, size_t n_sources, const double* src_xyz, const dou
         a.d_dst_index = nullptr;
         a.d_out = d_out.p;
         a.ld_out = n_dst;
+        a.max_block_steps = block_steps;
         btk_run(a, c.s);
         c.download(out, d_out.p, n * n_dst, "download");
         c.sync("sync");

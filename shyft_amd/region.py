@@ -394,9 +394,10 @@ def route(group_sums, group_uhgs, group_river, river_uhgs, river_downstream, dev
     return tuple(out)
 
 
-def btk(src_xyz, src_values, prior_gradient, btk_param, dst_xyz, device: int = -1) -> np.ndarray:
+def btk(src_xyz, src_values, prior_gradient, btk_param, dst_xyz, device: int = -1, block_steps: int = 0) -> np.ndarray:
     """Stateless Bayesian temperature kriging on the device (shyft_hip_btk): src_values [n][S] on the model axis,
-    prior_gradient [n], btk_param (gradient_sd C/m, sill, nugget, range, zscale), dst_xyz [D][3] -> [n][D]."""
+    prior_gradient [n], btk_param (gradient_sd C/m, sill, nugget, range, zscale), dst_xyz [D][3] -> [n][D].
+    block_steps caps the steps of one valid-source pattern per device product (0 = default; a test aid)."""
     L = lib()
     xyz = np.ascontiguousarray(src_xyz, dtype=np.float64).reshape(-1, 3)
     v = np.ascontiguousarray(src_values, dtype=np.float64).reshape(-1, xyz.shape[0])
@@ -404,8 +405,8 @@ def btk(src_xyz, src_values, prior_gradient, btk_param, dst_xyz, device: int = -
     p = np.ascontiguousarray(btk_param, dtype=np.float64).reshape(5)
     d = np.ascontiguousarray(dst_xyz, dtype=np.float64).reshape(-1, 3)
     out = np.empty((v.shape[0], d.shape[0]))
-    check(L.shyft_hip_btk(device, xyz.shape[0], _ptr(xyz), _ptr(v), v.shape[0], _ptr(g), _ptr(p), d.shape[0],
-                          _ptr(d), _ptr(out)), None)
+    check(L.shyft_hip_btk_blocked(device, xyz.shape[0], _ptr(xyz), _ptr(v), v.shape[0], _ptr(g), _ptr(p), d.shape[0],
+                                  _ptr(d), _ptr(out), int(block_steps)), None)
     return out
 
 
