@@ -832,7 +832,12 @@ int shyft_hip_route(int device, size_t n_groups, size_t T, const double* group_s
  * (calculated cell, member) pairs, member-fastest, each starting from the region's current state and
  * reading the region's forcing in place (shared, not copied). The region's own state and responses are
  * not modified. params[n_members][n_per_set] in the reference get/set order (as shyft_hip_set_parameters).
- * collect: SHYFT_HIP_COLLECT_DISCHARGE or SHYFT_HIP_COLLECT_DISCHARGE_SNOW (adds snow sca / swe). */
+ * collect: SHYFT_HIP_COLLECT_DISCHARGE or SHYFT_HIP_COLLECT_DISCHARGE_SNOW (adds snow sca / swe).
+ * Routed targets are batched too: routing.velocity / alpha / beta belong to the parameter vector, so every
+ * member has its own routing groups. shyft_hip_ensemble_group_sums reduces each member's groups of the last
+ * ensemble run and shyft_hip_route_members evaluates the shared river network for all members in
+ * 1 + 2 x levels launches; both give, bit for bit, what shyft_hip_routing_group_sums and shyft_hip_route give
+ * after a sequential run with the member's parameters. */
 int shyft_hip_ensemble_run(shyft_hip_region* h, const double* params, size_t n_members, size_t n_per_set,
                            int start_step, int n_steps, int collect);
 /* Sums of response `series` of the last ensemble run per member and catchment, steps [step0, step0+n)
@@ -843,6 +848,44 @@ int shyft_hip_ensemble_sums(const shyft_hip_region* h, int series, int area_weig
                             double* dst, int dst_on_device);
 /* Milliseconds of the last ensemble launch (HIP events on its stream). */
 double shyft_hip_ensemble_last_ms(const shyft_hip_region* h);
+/* Routing-group discharge sums of the last ensemble run, per member. group_of[n_members][n_cells] is the member's
+ * routing group of each cell, numbered from 0 within the member, -1 = the cell is not part of this evaluation;
+ * group_row[n_members + 1] gives each member's first row of dst[group_row[n_members]][n] (starts at 0, does not
+ * decrease). dst[group_row[m] + g][t] = sum of member m's avg_discharge over the cells of its group g, in cell
+ * order, steps [step0, step0 + n) inside the run's range: bit for bit shyft_hip_routing_group_sums of the same
+ * cells after a sequential run with the member's parameters (the segment sum adds by position within the segment).
+ * Refused before any launch: no ensemble run; n_members different from the run's; a group index outside the
+ * member's range; a cell with a group >= 0 that was not a calculated cell of the run; a sharded region (out of
+ * scope: evaluate the vectors one by one there). */
+int shyft_hip_ensemble_group_sums(const shyft_hip_region* h, size_t n_members, const int32_t* group_of,
+                                  const int64_t* group_row, size_t step0, size_t n, double* dst, int dst_on_device);
+/* p[n] doubles of device memory on the region's device, owned by the region and valid until the next call of this
+ * entry or the region's destruction: where a host caller keeps shyft_hip_ensemble_group_sums' rows (dst_on_device)
+ * for shyft_hip_route_members (src_on_device). Not for sharded regions. */
+int shyft_hip_ensemble_scratch(shyft_hip_region* h, size_t n, double** p);
+/* dst[n] (host) = the scratch rows [offset, offset + n): a host caller downloads only what it was asked for. */
+int shyft_hip_ensemble_scratch_read(const shyft_hip_region* h, size_t offset, size_t n, double* dst);
+/* shyft_hip_route for n_members independent sets of groups over one shared river network (stateless; device < 0 =
+ * current). Member m owns the global group rows [group_row[m], group_row[m+1]) of group_sums[G][T] (host or
+ * device), group_uhg[G][max_len], group_len[G] and group_river[G], G = group_row[n_members]; the river tables are
+ * those of shyft_hip_route. Outputs [n_members][R][T] (host or device); local and upstream may be null when not
+ * wanted. A member without groups gives zeros. The additions happen in shyft_hip_route's order, so member m's rows
+ * equal shyft_hip_route of its groups bit for bit. The argument checks of shyft_hip_route, and group_row must
+ * start at 0 and not decrease; all of them before the device is touched. */
+int shyft_hip_route_members(int device, size_t n_members, const int64_t* group_row, size_t T, const double* group_sums,
+                            int src_on_device, const double* group_uhg, const int32_t* group_len,
+                            const int32_t* group_river, size_t n_rivers, const double* river_uhg,
+                            const int32_t* river_len, const int32_t* river_downstream, size_t max_len, double* local,
+                            double* upstream, double* output, int dst_on_device);
+/* The definition of correct for shyft_hip_route_members: the literal loops on the host, in the reference's order
+ * (groups ascending within a river, taps ascending, upstream rivers ascending); host pointers only. */
+int shyft_hip_route_members_host(size_t n_members, const int64_t* group_row, size_t T, const double* group_sums,
+                                 const double* group_uhg, const int32_t* group_len, const int32_t* group_river,
+                                 size_t n_rivers, const double* river_uhg, const int32_t* river_len,
+                                 const int32_t* river_downstream, size_t max_len, double* local, double* upstream,
+                                 double* output);
+/* Milliseconds of the kernels of the last shyft_hip_route_members on the device (HIP events). */
+double shyft_hip_route_members_last_ms(int device);
 
 /* Diagnostic: evaluate one device elementary function (0 exp, 1 log, 2 pow(x, y), 3 lgamma,
  * 4 gamma_p(x, y)) on n host inputs on the current device; out[n] host. Used by the parity

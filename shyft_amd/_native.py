@@ -171,6 +171,17 @@ SIGNATURES = {
     "shyft_hip_ensemble_run": (C.c_int, [_h, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "shyft_hip_ensemble_sums": (C.c_int, [_h, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int]),
     "shyft_hip_ensemble_last_ms": (C.c_double, [_h]),
+    "shyft_hip_ensemble_group_sums": (C.c_int, [_h, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                C.c_void_p, C.c_int]),
+    "shyft_hip_ensemble_scratch": (C.c_int, [_h, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "shyft_hip_ensemble_scratch_read": (C.c_int, [_h, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "shyft_hip_route_members": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "shyft_hip_route_members_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "shyft_hip_route_members_last_ms": (C.c_double, [C.c_int]),
     "shyft_hip_math_selftest": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "shyft_hip_device_selftest": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
 }

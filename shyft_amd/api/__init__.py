@@ -1569,6 +1569,18 @@ class _ModelMixin:
     def river_output_flow_m3s(self, rid):
         return TimeSeries(self._time_axis, self._river_output_flow_m3s(rid), POINT_AVERAGE_VALUE)
 
+    def ensemble_river_output_flow_m3s(self, parameters, rids):
+        """MI355X addition: river_output_flow_m3s of the rivers `rids` for every parameter vector of `parameters`,
+        all vectors as one device ensemble (run and routing), each with the routing groups its own
+        routing.velocity / alpha / beta give. Starts from the model's current state and leaves the model's state,
+        parameters and responses untouched. Returns one list of TimeSeries (in `rids` order) per vector, each
+        bit-identical to set_region_parameter + run_cells + river_output_flow_m3s from the same state."""
+        rids = [int(r) for r in rids]
+        self._ensemble_run([p.to_vector() for p in parameters], False)
+        v = self._ensemble_routed(rids, 2)
+        return [[TimeSeries(self._time_axis, v[m, q], POINT_AVERAGE_VALUE) for q in range(len(rids))]
+                for m in range(len(parameters))]
+
     def river_upstream_inflow_m3s(self, rid):
         return TimeSeries(self._time_axis, self._river_upstream_inflow_m3s(rid), POINT_AVERAGE_VALUE)
 

@@ -103,7 +103,9 @@ class _Optimizer:
     set_parameter_ranges, set_verbose_level, establish_initial_state_from_model, get_initial_state,
     parameter_active, trace_size / trace_goal_function_value(s) / trace_parameter,
     target_specification, parameter_lower_bound / parameter_upper_bound.
-    MI355X addition: calculate_goal_functions(list of parameters) evaluates them as device ensembles."""
+    MI355X addition: calculate_goal_functions(list of parameters) evaluates them as device ensembles, routed
+    targets included (every member routed with its own routing.velocity / alpha / beta);
+    n_batched_evaluations / n_sequential_evaluations count the vectors evaluated each way."""
 
     _impl_t = None  # the C++ optimizer class of the stack
 
@@ -191,6 +193,16 @@ class _Optimizer:
     @batch_evaluation.setter
     def batch_evaluation(self, on):
         self._o.batch_evaluation = bool(on)
+
+    @property
+    def n_batched_evaluations(self):
+        """Parameter vectors evaluated as members of a device ensemble since set_target_specification."""
+        return self._o.n_batched_evaluations
+
+    @property
+    def n_sequential_evaluations(self):
+        """Parameter vectors evaluated one by one since set_target_specification."""
+        return self._o.n_sequential_evaluations
 
     # ---- evaluation and search
     def calculate_goal_function(self, parameters):

@@ -15,6 +15,8 @@
 #include <pybind11/stl.h>
 
 #include <cmath>
+#include <optional>
+#include <set>
 
 #include "calibration.hpp"
 #include "forecast.hpp"
@@ -245,6 +247,15 @@ void bind_model(py::module_& m, const char* name) {
         .def("_set_cell_routing", &M::set_cell_routing)
         .def("has_routing", &M::has_routing)
         .def("_river_output_flow_m3s", &M::river_output_flow_m3s)
+        .def("_ensemble_run", &M::ensemble_run, py::call_guard<py::gil_scoped_release>())
+        .def("_ensemble_last_ms", &M::ensemble_last_ms)
+        .def("_ensemble_routed", [](const M& x, const std::vector<int64_t>& rids, int which) {
+            auto v = x.ensemble_routed(rids, which);
+            const size_t T = x.time_axis.size();
+            py::array_t<double> a({T ? v.size() / (T * std::max<size_t>(1, rids.size())) : size_t(0), rids.size(), T});
+            std::copy(v.begin(), v.end(), a.mutable_data());
+            return a;
+        }, py::arg("rids"), py::arg("which") = 2)
         .def("_river_upstream_inflow_m3s", &M::river_upstream_inflow_m3s)
         .def("_river_local_inflow_m3s", &M::river_local_inflow_m3s);
 }
@@ -265,6 +276,8 @@ void bind_optimizer(py::module_& m, const char* name) {
         .def_readwrite("_upper", &O::parameter_upper_bound)
         .def_readwrite("batch_evaluation", &O::batch_evaluation)
         .def_readwrite("max_batch_members", &O::max_batch_members)
+        .def_readonly("n_batched_evaluations", &O::n_batched_evaluations)
+        .def_readonly("n_sequential_evaluations", &O::n_sequential_evaluations)
         .def("establish_initial_state_from_model", &O::establish_initial_state_from_model)
         .def("_get_initial_state", &O::get_initial_state)
         .def("set_verbose_level", &O::set_verbose_level, py::arg("level"))
@@ -825,6 +838,27 @@ PYBIND11_MODULE(_api, m) {
         .def("set_downstream_by_id", &river_network::set_downstream_by_id)
         .def("network_contains_directed_cycle", &river_network::network_contains_directed_cycle);
     m.def("make_uhg_from_gamma", &make_uhg_from_gamma, py::arg("n_steps"), py::arg("alpha"), py::arg("beta"));
+    // the routing groups one (velocity, alpha, beta) gives the cells (host only): (group of each cell, river id and
+    // UHG weights of each group); rivers restricts the groups to cells routed to those rivers
+    m.def(
+        "routing_groups",
+        [](const std::vector<int64_t>& cell_rid, const std::vector<double>& cell_distance, double dt, double velocity,
+           double alpha, double beta, const std::optional<std::vector<int64_t>>& only) {
+            if (cell_rid.size() != cell_distance.size()) throw std::runtime_error("routing_groups: one distance per cell");
+            std::set<int64_t> net;
+            if (only) net.insert(only->begin(), only->end());
+            const auto rg = make_routing_groups_of(uhg_parameter(velocity, alpha, beta), cell_rid, cell_distance, to_us(dt),
+                                                   only ? &net : nullptr);
+            std::vector<int64_t> rid;
+            std::vector<std::vector<double>> w;
+            for (const auto& g : rg.groups) {
+                rid.push_back(g.rid);
+                w.push_back(g.w);
+            }
+            return py::make_tuple(rg.group_of, rid, w);
+        },
+        py::arg("cell_rid"), py::arg("cell_distance"), py::arg("dt"), py::arg("velocity"), py::arg("alpha") = 7.0,
+        py::arg("beta") = 0.0, py::arg("rivers") = py::none());
 
     m.def("utc_time", [](int y, int mo, int d, int h, int mi, int s) { return to_s(utc_time(y, mo, d, h, mi, s)); });
     m.def("average_values", [](const point_ts& s, const fixed_dt& ta) {

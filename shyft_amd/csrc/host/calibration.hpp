@@ -11,6 +11,9 @@
 // and the catchment sums of all members come back from one segmented reduction. The goal value of a
 // member is bit-identical to the value of a sequential run with the same vector (same kernel arithmetic
 // per lane, same fixed-order catchment reduction), so batching changes wall time, never results.
+// ROUTED_DISCHARGE targets are batched like the others: every member is routed with the routing groups its
+// own routing.velocity / alpha / beta give (region_model::ensemble_routed), the additions in the sequential
+// path's order; where that would refuse the vectors are evaluated one by one.
 //
 // Random streams: sceua and dream draw from std::default_random_engine through
 // uniform_real_distribution<double>(0,1), default seeded per call, exactly as the reference
@@ -902,6 +905,8 @@ class optimizer {
     // MI355X: evaluate independent parameter vectors as one device ensemble launch (bit-identical goals)
     bool batch_evaluation = true;
     size_t max_batch_members = 512;  // members per ensemble launch (bounds device memory: members x cells x T)
+    // parameter vectors evaluated as ensemble members / one by one since set_target_specification
+    size_t n_batched_evaluations = 0, n_sequential_evaluations = 0;
 
     optimizer(M& m, const std::vector<target_specification>& targets_, const parameter_t& p_min, const parameter_t& p_max)
         : model(m), targets(targets_) {
@@ -920,6 +925,7 @@ class optimizer {
         targets = t;
         parameter_lower_bound = lo;
         parameter_upper_bound = hi;
+        n_batched_evaluations = n_sequential_evaluations = 0;
         prepare_optimize();
     }
     void set_parameter_ranges(const parameter_t& p_min, const parameter_t& p_max) {
@@ -1076,6 +1082,7 @@ class optimizer {
     // per-run catchment aggregates the targets read (one member of an ensemble, or the model's own run)
     struct run_sums {
         std::function<const double*(size_t cix)> discharge, charge, sca_area, swe_area;
+        std::function<std::vector<double>(int64_t rid)> routed;  // river_output_flow_m3s of the run
     };
     bool need(target_property_type p) const {
         for (const auto& t : targets)
@@ -1119,7 +1126,7 @@ class optimizer {
                     break;
                 }
                 case ROUTED_DISCHARGE:
-                    sum = model.river_output_flow_m3s(t.river_id);
+                    sum = s.routed(t.river_id);
                     break;
             }
             const point_ts prop(model.time_axis, std::move(sum), POINT_AVERAGE_VALUE);
@@ -1166,15 +1173,25 @@ class optimizer {
         if (need(SNOW_COVERED_AREA)) sca = model.catchment_area_sums(2);
         if (need(SNOW_WATER_EQUIVALENT)) swe = model.catchment_area_sums(3);
         run_sums s{[&](size_t c) { return q[c].data(); }, [&](size_t c) { return ch[c].data(); },
-                   [&](size_t c) { return sca[c].data(); }, [&](size_t c) { return swe[c].data(); }};
+                   [&](size_t c) { return sca[c].data(); }, [&](size_t c) { return swe[c].data(); },
+                   [&](int64_t rid) { return model.river_output_flow_m3s(rid); }};
         const double g = goal_of(s);
         trace(p, g);
+        ++n_sequential_evaluations;
         return g;
     }
     // a batch of full parameter vectors: device ensembles where the targets allow, else one by one
     std::vector<double> run_full_batch(const std::vector<parameter_t>& fulls) {
         std::vector<double> r;
-        if (!batch_evaluation || fulls.size() < 2 || need(ROUTED_DISCHARGE)) {
+        // routed targets: the union of their rivers, evaluated once per ensemble for all members. Where
+        // ensemble_routed would refuse (a sharded region, a feeding cell that is not calculated or has a
+        // catchment-specific parameter) the vectors go one by one; prepare_optimize rules the last two out.
+        std::vector<int64_t> rids;
+        for (const auto& t : targets)
+            if (t.catchment_property == ROUTED_DISCHARGE && std::find(rids.begin(), rids.end(), t.river_id) == rids.end())
+                rids.push_back(t.river_id);
+        const bool routed = !rids.empty() && model.has_routing();
+        if (!batch_evaluation || fulls.size() < 2 || (routed && !model.ensemble_routed_refusal(rids).empty())) {
             for (const auto& p : fulls) r.push_back(run_full(p));
             return r;
         }
@@ -1190,12 +1207,20 @@ class optimizer {
             if (need(CELL_CHARGE)) ch = model.ensemble_sums(1, false);
             if (need(SNOW_COVERED_AREA)) sca = model.ensemble_sums(2, true);
             if (need(SNOW_WATER_EQUIVALENT)) swe = model.ensemble_sums(3, true);
+            std::vector<double> rq;  // [member][rids][T]
+            if (need(ROUTED_DISCHARGE)) rq = model.ensemble_routed(rids);
             for (size_t k = 0; k < members.size(); ++k) {
                 const size_t o = k * C * T;
                 run_sums s{[&](size_t c) { return q.data() + o + c * T; }, [&](size_t c) { return ch.data() + o + c * T; },
-                           [&](size_t c) { return sca.data() + o + c * T; }, [&](size_t c) { return swe.data() + o + c * T; }};
+                           [&](size_t c) { return sca.data() + o + c * T; }, [&](size_t c) { return swe.data() + o + c * T; },
+                           [&](int64_t rid) {
+                               const size_t j = size_t(std::find(rids.begin(), rids.end(), rid) - rids.begin());
+                               const double* v = rq.data() + (k * rids.size() + j) * T;
+                               return std::vector<double>(v, v + T);
+                           }};
                 const double g = goal_of(s);
                 trace(members[k], g);
+                ++n_batched_evaluations;
                 r.push_back(g);
             }
         }

@@ -789,6 +789,88 @@ class region_model {
                                         collect_snow ? SHYFT_HIP_COLLECT_DISCHARGE_SNOW : SHYFT_HIP_COLLECT_DISCHARGE),
                  h_.get());
         ens_members_ = members.size();
+        ens_routing_.clear();
+        for (const auto& p : members) ens_routing_.push_back(routing_triple(p));
+    }
+    // milliseconds of the last ensemble launch (shyft_hip_ensemble_last_ms)
+    double ensemble_last_ms() const { return shyft_hip_ensemble_last_ms(h_.get()); }
+    // Why ensemble_routed(rids) would refuse, or "" when it would not: the callers that have a sequential path
+    // (the optimizer) ask first and never get a different number silently.
+    std::string ensemble_routed_refusal(const std::vector<int64_t>& rids) const {
+        if (!has_routing()) return "";
+        if (shard_devices().size() > 1)
+            return "ensemble_routed: sharded regions are out of scope; evaluate the parameter vectors one by one";
+        const std::set<int64_t> net = sub_network(rids);
+        for (size_t i = 0; i < size(); ++i) {
+            const auto& g = geo_[i];
+            if (!valid_routing_id(g.routing.id)) continue;
+            rivers.check_rid(g.routing.id);
+            if (net.find(g.routing.id) == net.end()) continue;
+            if (!is_calculated_by_catchment_ix(catchment_ix_of_cell(i)))
+                return "ensemble_routed: cell " + std::to_string(i) + " of catchment " + std::to_string(g.catchment_id()) +
+                       " routes to river " + std::to_string(g.routing.id) +
+                       " but is not calculated; include the catchment in the calculation filter";
+            if (has_catchment_parameter(g.catchment_id()))
+                return "ensemble_routed: catchment " + std::to_string(g.catchment_id()) + " feeding river " +
+                       std::to_string(g.routing.id) +
+                       " has a catchment-specific parameter; members replace the region parameter only, remove it first";
+        }
+        return "";
+    }
+    // [member][rid][t] of the last ensemble run: routing::model::output_m3s (which = 2; 0 local_inflow, 1
+    // upstream_inflow) of the rivers `rids`, every member with its own routing groups, evaluated for those rivers
+    // and everything upstream of them only. Bit-identical to routed(rid, which) after a sequential run with the
+    // member's region parameter. Zeros on a model without routing.
+    std::vector<double> ensemble_routed(const std::vector<int64_t>& rids, int which = 2) const {
+        const size_t T = time_axis.size(), P = ens_members_, Q = rids.size();
+        if (P == 0 || ens_routing_.size() != P) throw std::runtime_error("ensemble_routed: no ensemble run");
+        std::vector<double> res(P * Q * T, 0.0);
+        if (!has_routing() || Q == 0 || T == 0) return res;
+        for (auto rid : rids) rivers.check_rid(rid);
+        const std::string refusal = ensemble_routed_refusal(rids);
+        if (!refusal.empty()) throw std::runtime_error(refusal);
+        const std::set<int64_t> net = sub_network(rids);
+        std::vector<int64_t> cell_rid;
+        std::vector<double> cell_distance;
+        cell_routing(cell_rid, cell_distance);
+        const size_t N = size();
+        std::vector<routing_groups> rg;
+        std::vector<const std::vector<uhg_group>*> lists;
+        std::vector<int32_t> group_of(P * N);
+        std::vector<int64_t> group_row(P + 1, 0);
+        rg.reserve(P);
+        for (size_t m = 0; m < P; ++m) {
+            rg.push_back(make_routing_groups_of(ens_routing_[m], cell_rid, cell_distance, time_axis.dt, &net));
+            std::copy(rg[m].group_of.begin(), rg[m].group_of.end(), group_of.begin() + m * N);
+            group_row[m + 1] = group_row[m] + int64_t(rg[m].groups.size());
+        }
+        for (const auto& g : rg) lists.push_back(&g.groups);
+        const route_tables rt = make_route_tables(&net, lists);
+        const size_t R = rt.ids.size(), G = size_t(group_row[P]);
+        // the group sums stay on the device between the reduction and the network evaluation, and so do the river
+        // series that were not asked for
+        double* d = nullptr;
+        const size_t n_out = which == 2 ? 1 : 2;  // output_m3s is always computed
+        throw_if(shyft_hip_ensemble_scratch(h_.get(), G * T + n_out * P * R * T, &d), h_.get());
+        double* d_sums = d;
+        double* d_sel = d + G * T;  // the series asked for
+        double* d_out = which == 2 ? d_sel : d_sel + P * R * T;
+        throw_if(shyft_hip_ensemble_group_sums(h_.get(), P, group_of.data(), group_row.data(), 0, T, d_sums, 1), h_.get());
+        int device = -1;
+        shyft_hip_region_shards(h_.get(), 0, &device, nullptr, nullptr);
+        throw_if(shyft_hip_route_members(device, P, group_row.data(), T, d_sums, 1, rt.gw.data(), rt.glen.data(),
+                                         rt.griver.data(), R, rt.rwf.data(), rt.rlen.data(), rt.rdown.data(), rt.max_len,
+                                         which == 0 ? d_sel : nullptr, which == 1 ? d_sel : nullptr,
+                                         d_out, 1),
+                 nullptr);
+        for (size_t m = 0; m < P; ++m)
+            for (size_t q = 0; q < Q; ++q) {
+                const size_t r = size_t(rt.index_of.at(rids[q]));
+                throw_if(shyft_hip_ensemble_scratch_read(h_.get(), size_t(d_sel - d) + (m * R + r) * T, T,
+                                                         res.data() + (m * Q + q) * T),
+                         h_.get());
+            }
+        return res;
     }
     // [member][catchment][t] sums (area_weighted: of value x cell area) of the last ensemble run
     std::vector<double> ensemble_sums(int series, bool area_weighted) const {
@@ -836,6 +918,17 @@ class region_model {
     std::vector<bool> state_collection_, snow_collection_;
     mutable bool routing_dirty_ = true;
     size_t ens_members_ = 0;
+    std::vector<uhg_parameter> ens_routing_;  // (velocity, alpha, beta) of the last ensemble run's members
+
+    // the rivers `rids` and everything upstream of them
+    std::set<int64_t> sub_network(const std::vector<int64_t>& rids) const {
+        std::set<int64_t> net;
+        for (auto rid : rids) {
+            net.insert(rid);
+            for (auto u : rivers.all_upstreams_by_id(rid)) net.insert(u);
+        }
+        return net;
+    }
 
     static double pot_ratio(double q_m3s, double area_m2, double scale_factor) {
         const double water_level = q_m3s * (3600.0 * 1000.0) / area_m2;  // m3s_to_mmh (unit_conversion.h:12-15)
@@ -973,67 +1066,95 @@ class region_model {
         const size_t T = time_axis.size();
         if (!has_routing()) return std::vector<double>(T, 0.0);
         rivers.check_rid(rid);
-        // routing groups: cells sharing (river, UHG length, alpha, beta) (routing.h:326-330)
-        std::vector<uhg_group> groups;
-        std::vector<int32_t> group_of(size(), -1);
-        std::map<std::tuple<int64_t, int, double, double>, size_t> key_to_group;
-        for (size_t i = 0; i < size(); ++i) {
-            const auto& g = geo_[i];
-            if (!valid_routing_id(g.routing.id)) continue;
-            // every cell routed to the river counts, whatever the catchment calculation filter says:
-            // routing::model::local_inflow (routing.h:345-350) iterates all cells; a filtered-out cell
-            // contributes the response series it holds (the last run that included it), as in the reference
-            rivers.check_rid(g.routing.id);  // routing::model::verify_cell_river_connections (routing.h:313-320)
-            const auto& p = cell_parameter(i);
-            const double velocity = p[Stack::k_routing], alpha = p[Stack::k_routing + 1], beta = p[Stack::k_routing + 2];
-            const int n_steps = uhg_steps(g.routing.distance, velocity, time_axis.dt);
-            auto key = std::make_tuple(g.routing.id, n_steps, alpha, beta);
-            auto f = key_to_group.find(key);
-            if (f == key_to_group.end()) {
-                f = key_to_group.emplace(key, groups.size()).first;
-                groups.push_back(uhg_group{g.routing.id, make_uhg_from_gamma(n_steps, alpha, beta), {}});
-            }
-            group_of[i] = int32_t(f->second);
-        }
+        // routing groups: cells sharing (river, UHG length, alpha, beta) (routing.h:326-330).
+        // Every cell routed to a river counts, whatever the catchment calculation filter says:
+        // routing::model::local_inflow (routing.h:345-350) iterates all cells; a filtered-out cell
+        // contributes the response series it holds (the last run that included it), as in the reference
+        std::vector<int64_t> cell_rid;
+        std::vector<double> cell_distance;
+        cell_routing(cell_rid, cell_distance);
+        const routing_groups rg = make_routing_groups(cell_rid, cell_distance, time_axis.dt, [this](size_t i) {
+            return routing_triple(cell_parameter(i));
+        });
+        const std::vector<uhg_group>& groups = rg.groups;
+        const std::vector<int32_t>& group_of = rg.group_of;
         const size_t G = groups.size();
         std::vector<double> sums(G * T);
         throw_if(shyft_hip_set_routing_groups(h_.get(), group_of.data(), G), h_.get());
         if (G) throw_if(shyft_hip_routing_group_sums(h_.get(), 0, T, sums.data(), 0), h_.get());
-        // rivers indexed in ascending id (the rid_map order)
-        std::vector<int64_t> ids;
-        std::map<int64_t, int32_t> index_of;
-        for (const auto& kv : rivers.rid_map) {
-            index_of[kv.first] = int32_t(ids.size());
-            ids.push_back(kv.first);
-        }
-        const size_t R = ids.size();
-        std::vector<std::vector<double>> rw(R);
-        size_t max_len = 1;
-        for (size_t r = 0; r < R; ++r) {
-            rw[r] = rivers.rid_map.at(ids[r]).uhg(time_axis.dt);
-            max_len = std::max(max_len, rw[r].size());
-        }
-        for (const auto& g : groups) max_len = std::max(max_len, g.w.size());
-        std::vector<double> gw(G * max_len, 0.0), rwf(R * max_len, 0.0);
-        std::vector<int32_t> glen(G), griver(G), rlen(R), rdown(R);
-        for (size_t k = 0; k < G; ++k) {
-            std::copy(groups[k].w.begin(), groups[k].w.end(), gw.begin() + k * max_len);
-            glen[k] = int32_t(groups[k].w.size());
-            griver[k] = index_of.at(groups[k].rid);
-        }
-        for (size_t r = 0; r < R; ++r) {
-            std::copy(rw[r].begin(), rw[r].end(), rwf.begin() + r * max_len);
-            rlen[r] = int32_t(rw[r].size());
-            const int64_t ds = rivers.rid_map.at(ids[r]).downstream_id;
-            rdown[r] = valid_routing_id(ds) ? index_of.at(ds) : -1;
-        }
+        const route_tables rt = make_route_tables(nullptr, {&groups});
+        const size_t R = rt.ids.size();
         std::vector<double> local(R * T), up(R * T), out(R * T);
-        throw_if(shyft_hip_route(-1, G, T, sums.data(), 0, gw.data(), glen.data(), griver.data(), R, rwf.data(),
-                                 rlen.data(), rdown.data(), max_len, local.data(), up.data(), out.data(), 0),
+        throw_if(shyft_hip_route(-1, G, T, sums.data(), 0, rt.gw.data(), rt.glen.data(), rt.griver.data(), R,
+                                 rt.rwf.data(), rt.rlen.data(), rt.rdown.data(), rt.max_len, local.data(), up.data(),
+                                 out.data(), 0),
                  nullptr);
         const auto& sel = which == 0 ? local : (which == 1 ? up : out);
-        const size_t r = size_t(index_of.at(rid));
+        const size_t r = size_t(rt.index_of.at(rid));
         return std::vector<double>(sel.begin() + r * T, sel.begin() + (r + 1) * T);
+    }
+
+    static uhg_parameter routing_triple(const parameter_t& p) {
+        return uhg_parameter(p[Stack::k_routing], p[Stack::k_routing + 1], p[Stack::k_routing + 2]);
+    }
+    // river id and routing distance of every cell; routing::model::verify_cell_river_connections (routing.h:313-320)
+    void cell_routing(std::vector<int64_t>& rid, std::vector<double>& distance) const {
+        rid.resize(size());
+        distance.resize(size());
+        for (size_t i = 0; i < size(); ++i) {
+            rid[i] = geo_[i].routing.id;
+            distance[i] = geo_[i].routing.distance;
+            if (valid_routing_id(rid[i])) rivers.check_rid(rid[i]);
+        }
+    }
+    // The flat tables shyft_hip_route / shyft_hip_route_members take: the rivers (all, or those of `only`) indexed in
+    // ascending id (the rid_map order) with their UHGs and downstream indices, and the UHG rows of the group lists
+    // laid end to end (one list for routed(), one per member for ensemble_routed()).
+    struct route_tables {
+        std::vector<int64_t> ids;
+        std::map<int64_t, int32_t> index_of;
+        size_t max_len = 1;
+        std::vector<double> gw, rwf;
+        std::vector<int32_t> glen, griver, rlen, rdown;
+    };
+    route_tables make_route_tables(const std::set<int64_t>* only, const std::vector<const std::vector<uhg_group>*>& lists) const {
+        route_tables rt;
+        for (const auto& kv : rivers.rid_map) {
+            if (only && only->find(kv.first) == only->end()) continue;
+            rt.index_of[kv.first] = int32_t(rt.ids.size());
+            rt.ids.push_back(kv.first);
+        }
+        const size_t R = rt.ids.size();
+        std::vector<std::vector<double>> rw(R);
+        for (size_t r = 0; r < R; ++r) {
+            rw[r] = rivers.rid_map.at(rt.ids[r]).uhg(time_axis.dt);
+            rt.max_len = std::max(rt.max_len, rw[r].size());
+        }
+        size_t G = 0;
+        for (const auto* l : lists) {
+            G += l->size();
+            for (const auto& g : *l) rt.max_len = std::max(rt.max_len, g.w.size());
+        }
+        rt.gw.assign(G * rt.max_len, 0.0);
+        rt.rwf.assign(R * rt.max_len, 0.0);
+        rt.glen.resize(G); rt.griver.resize(G); rt.rlen.resize(R); rt.rdown.resize(R);
+        size_t k = 0;
+        for (const auto* l : lists)
+            for (const auto& g : *l) {
+                std::copy(g.w.begin(), g.w.end(), rt.gw.begin() + k * rt.max_len);
+                rt.glen[k] = int32_t(g.w.size());
+                rt.griver[k] = rt.index_of.at(g.rid);
+                ++k;
+            }
+        for (size_t r = 0; r < R; ++r) {
+            std::copy(rw[r].begin(), rw[r].end(), rt.rwf.begin() + r * rt.max_len);
+            rt.rlen[r] = int32_t(rw[r].size());
+            const int64_t ds = rivers.rid_map.at(rt.ids[r]).downstream_id;
+            // a sub-network is closed upstream, so a downstream river outside it is simply not evaluated
+            const auto f = valid_routing_id(ds) ? rt.index_of.find(ds) : rt.index_of.end();
+            rt.rdown[r] = f != rt.index_of.end() ? f->second : -1;
+        }
+        return rt;
     }
 
     void clone_from(const region_model& o, bool full_collection) {

@@ -19,8 +19,10 @@
 #include <cmath>
 #include <cstdint>
 #include <map>
+#include <set>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../../detmath/detmath.h"
@@ -191,5 +193,43 @@ struct uhg_group {
     std::vector<double> w;
     std::vector<double> q;
 };
+
+// The routing groups of a set of cells: cells sharing (river, UHG steps, alpha, beta) (routing.h:326-330), numbered
+// by first appearance in cell order. group_of[i] = -1: the cell is not routed, or its river is not in `only`.
+struct routing_groups {
+    std::vector<uhg_group> groups;  // rid and w; q is left empty
+    std::vector<int32_t> group_of;  // per cell
+};
+
+// triple_of(i) gives the cell's (velocity, alpha, beta). `only` (when not null) restricts the groups to cells routed
+// to those rivers; a restriction keeps the relative order of every river's groups, because a river's groups are
+// numbered by the first cell of each in cell order whichever other rivers take part.
+template <class TripleOf>
+inline routing_groups make_routing_groups(const std::vector<int64_t>& cell_rid, const std::vector<double>& cell_distance,
+                                          utctimespan dt, TripleOf&& triple_of, const std::set<int64_t>* only = nullptr) {
+    routing_groups r;
+    r.group_of.assign(cell_rid.size(), -1);
+    std::map<std::tuple<int64_t, int, double, double>, size_t> key_to_group;
+    for (size_t i = 0; i < cell_rid.size(); ++i) {
+        if (!valid_routing_id(cell_rid[i])) continue;
+        if (only && only->find(cell_rid[i]) == only->end()) continue;
+        const uhg_parameter p = triple_of(i);
+        const int n_steps = uhg_steps(cell_distance[i], p.velocity, dt);
+        const auto key = std::make_tuple(cell_rid[i], n_steps, p.alpha, p.beta);
+        auto f = key_to_group.find(key);
+        if (f == key_to_group.end()) {
+            f = key_to_group.emplace(key, r.groups.size()).first;
+            r.groups.push_back(uhg_group{cell_rid[i], make_uhg_from_gamma(n_steps, p.alpha, p.beta), {}});
+        }
+        r.group_of[i] = int32_t(f->second);
+    }
+    return r;
+}
+// one (velocity, alpha, beta) for every cell: a region parameter vector, as a calibration member has
+inline routing_groups make_routing_groups_of(const uhg_parameter& p, const std::vector<int64_t>& cell_rid,
+                                             const std::vector<double>& cell_distance, utctimespan dt,
+                                             const std::set<int64_t>* only = nullptr) {
+    return make_routing_groups(cell_rid, cell_distance, dt, [&p](size_t) { return p; }, only);
+}
 
 }  // namespace shyft_hip::host

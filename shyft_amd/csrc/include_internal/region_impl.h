@@ -148,6 +148,8 @@ struct shyft_hip_region {
     const shyft_hip_region* forcing_src = nullptr;  // set on an ensemble lane region: whose forcing it reads
     dbuf<int32_t> d_fcol;                            // [lanes] forcing column (cell of the parent region)
     size_t ens_members = 0, ens_cells = 0, ens_groups = 0, ens_b = 0, ens_e = 0;
+    std::vector<int32_t> ens_k_of_cell;  // [n] the cell's rank among the calculated cells of the last ensemble run, -1 = none
+    dbuf<double> d_ens_scratch;          // shyft_hip_ensemble_scratch: the caller's device rows between two ensemble entries
 
     bool hbv() const { return stack == SHYFT_HIP_HBV_STACK; }
     bool ptssk() const { return stack == SHYFT_HIP_PT_SS_K; }

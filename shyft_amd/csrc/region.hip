@@ -1928,6 +1928,8 @@ int shyft_hip_ensemble_run(shyft_hip_region* h, const double* params, size_t n_m
         h->ens_cells = K;
         h->ens_b = b;
         h->ens_e = e;
+        h->ens_k_of_cell.assign(h->n, -1);
+        for (size_t k = 0; k < K; ++k) h->ens_k_of_cell[size_t(cells[k])] = int32_t(k);
         launch_run(x, int(b), int(e - b));
         finish_run(x);
     });
@@ -1958,6 +1960,89 @@ int shyft_hip_ensemble_sums(const shyft_hip_region* hc, int series, int area_wei
                   "ensemble sums");
         if (!dst_on_device) copy_rows(x->stream, dst, out, G * n * sizeof(double), 0, 1);
         else hip_check(hipStreamSynchronize(x->stream), "sync");
+    });
+}
+
+int shyft_hip_ensemble_group_sums(const shyft_hip_region* hc, size_t n_members, const int32_t* group_of,
+                                  const int64_t* group_row, size_t step0, size_t n, double* dst, int dst_on_device) {
+    shyft_hip_region* h = const_cast<shyft_hip_region*>(hc);
+    if (!h || !group_of || !group_row) return fail(h, "shyft_hip_ensemble_group_sums: null argument");
+    if (h->sh)
+        return fail(h, "ensemble_group_sums: sharded regions are out of scope (route each vector with "
+                       "shyft_hip_routing_group_sums instead)");
+    return guarded(h, [&] {
+        shyft_hip_region* x = h->ens;
+        if (!x || h->ens_members == 0) throw std::runtime_error("ensemble_group_sums: no ensemble run");
+        const size_t P = h->ens_members, N = h->n, L = x->n;
+        if (n_members != P)
+            throw std::runtime_error("ensemble_group_sums: n_members differs from the last ensemble run's " + std::to_string(P));
+        if (step0 < h->ens_b || step0 + n > h->ens_e)
+            throw std::runtime_error("ensemble_group_sums: steps outside the last ensemble run");
+        if (group_row[0] != 0) throw std::runtime_error("ensemble_group_sums: group_row must start at 0");
+        for (size_t m = 0; m < P; ++m)
+            if (group_row[m + 1] < group_row[m]) throw std::runtime_error("ensemble_group_sums: group_row must not decrease");
+        const size_t G = size_t(group_row[P]);
+        // one segment per (member, group): its lanes k * P + m in cell order
+        std::vector<int32_t> off(G + 1, 0);
+        size_t n_lanes = 0;
+        for (size_t m = 0; m < P; ++m) {
+            const int64_t Gm = group_row[m + 1] - group_row[m];
+            for (size_t i = 0; i < N; ++i) {
+                const int32_t g = group_of[m * N + i];
+                if (g == -1) continue;
+                if (g < -1 || int64_t(g) >= Gm) throw std::runtime_error("ensemble_group_sums: group index out of range");
+                if (h->ens_k_of_cell[i] < 0)
+                    throw std::runtime_error("ensemble_group_sums: cell " + std::to_string(i) +
+                                             " has a group but was not a calculated cell of the ensemble run");
+                off[size_t(group_row[m] + g) + 1]++;
+                ++n_lanes;
+            }
+        }
+        if (G == 0 || n == 0) return;
+        if (!dst) throw std::runtime_error("ensemble_group_sums: dst is null");
+        for (size_t s = 0; s < G; ++s) off[s + 1] += off[s];  // n_lanes <= P * K = L <= INT32_MAX
+        std::vector<int32_t> lanes(std::max<size_t>(1, n_lanes)), pos(off.begin(), off.end() - 1);
+        for (size_t m = 0; m < P; ++m)
+            for (size_t i = 0; i < N; ++i) {
+                const int32_t g = group_of[m * N + i];
+                if (g >= 0) lanes[size_t(pos[size_t(group_row[m] + g)]++)] = int32_t(size_t(h->ens_k_of_cell[i]) * P + m);
+            }
+        x->d_rseg_off.alloc(off.size());
+        x->d_rseg_cells.alloc(lanes.size());
+        hip_check(hipMemcpy(x->d_rseg_off.p, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice), "upload");
+        hip_check(hipMemcpy(x->d_rseg_cells.p, lanes.data(), lanes.size() * sizeof(int32_t), hipMemcpyHostToDevice), "upload");
+        const double* src = x->d_resp.p + (size_t(SHYFT_HIP_AVG_DISCHARGE) * x->TW + (step0 - x->w0)) * L;
+        double* out = dst;
+        if (!dst_on_device) {
+            x->d_tmp.alloc(std::max(x->d_tmp.n, G * n));
+            out = x->d_tmp.p;
+        }
+        constexpr size_t SLICE = 65535;  // segments go in grid.y
+        for (size_t s0 = 0; s0 < G; s0 += SLICE)
+            hip_check(launch_segment_sums(src, L, n, x->d_rseg_cells.p, x->d_rseg_off.p + s0, std::min(SLICE, G - s0),
+                                          out + s0 * n, x->stream),
+                      "ensemble group sums");
+        if (!dst_on_device) copy_rows(x->stream, dst, out, G * n * sizeof(double), 0, 1);
+        else hip_check(hipStreamSynchronize(x->stream), "sync");
+    });
+}
+
+int shyft_hip_ensemble_scratch(shyft_hip_region* h, size_t n, double** p) {
+    if (!h || !p) return fail(h, "shyft_hip_ensemble_scratch: null argument");
+    if (h->sh) return fail(h, "ensemble_scratch: sharded regions are out of scope");
+    return guarded(h, [&] {
+        if (h->d_ens_scratch.n < n) h->d_ens_scratch.alloc(n);
+        *p = h->d_ens_scratch.p;
+    });
+}
+
+int shyft_hip_ensemble_scratch_read(const shyft_hip_region* hc, size_t offset, size_t n, double* dst) {
+    shyft_hip_region* h = const_cast<shyft_hip_region*>(hc);
+    if (!h || !dst) return fail(h, "shyft_hip_ensemble_scratch_read: null argument");
+    return guarded(h, [&] {
+        if (offset > h->d_ens_scratch.n || n > h->d_ens_scratch.n - offset)
+            throw std::runtime_error("ensemble_scratch_read: range outside the scratch rows");
+        if (n) hip_check(hipMemcpy(dst, h->d_ens_scratch.p + offset, n * sizeof(double), hipMemcpyDeviceToHost), "download");
     });
 }
 

@@ -363,6 +363,21 @@ class HipRegion:
     def ensemble_last_ms(self) -> float:
         return float(self._L.shyft_hip_ensemble_last_ms(self.h))
 
+    def ensemble_group_sums(self, group_of, group_row, step0: int, n: int, dev_ptr=None):
+        """Routing-group discharge sums of the last ensemble run (shyft_hip_ensemble_group_sums): group_of
+        [n_members][n_cells] (-1 = not part of this evaluation), group_row [n_members + 1]. Returns
+        [group_row[-1]][n], or writes it to dev_ptr."""
+        g = np.ascontiguousarray(group_of, dtype=np.int32)
+        row = np.ascontiguousarray(group_row, dtype=np.int64)
+        assert g.ndim == 2 and g.shape[1] == self.n and row.shape == (g.shape[0] + 1,)
+        if dev_ptr is not None:
+            self._chk(self._L.shyft_hip_ensemble_group_sums(self.h, g.shape[0], _ptr(g), _ptr(row), step0, n,
+                                                            C.c_void_p(dev_ptr), 1))
+            return None
+        out = np.empty((max(int(row[-1]), 0), n), dtype=np.float64)
+        self._chk(self._L.shyft_hip_ensemble_group_sums(self.h, g.shape[0], _ptr(g), _ptr(row), step0, n, _ptr(out), 0))
+        return out
+
 
 def route(group_sums, group_uhgs, group_river, river_uhgs, river_downstream, device: int = -1, sums_dev_ptr=None,
           T: int | None = None):
@@ -392,6 +407,51 @@ def route(group_sums, group_uhgs, group_river, river_uhgs, river_downstream, dev
     check(L.shyft_hip_route(device, G, T, src, on_dev, _ptr(gw), _ptr(glen), _ptr(gr), R, _ptr(rw), _ptr(rlen),
                             _ptr(rd), max_len, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), 0), None)
     return tuple(out)
+
+
+def route_members(group_row, group_sums, group_uhgs, group_river, river_uhgs, river_downstream, device: int = -1,
+                  host: bool = False, sums_dev_ptr=None, T: int | None = None, max_len: int | None = None):
+    """River network evaluation for members with their own routing groups (shyft_hip_route_members; host=True: its
+    _host twin, the literal loops). Member m owns the global group rows [group_row[m], group_row[m+1]) of group_sums
+    [G][T] (numpy, or sums_dev_ptr + T on the device), group_uhgs and group_river; the rivers are shared. Returns
+    (local, upstream, output), each [n_members][R][T]."""
+    L = lib()
+    row = np.ascontiguousarray(group_row, dtype=np.int64)
+    P, G, R = row.size - 1, len(group_uhgs), len(river_uhgs)
+    width = max([1] + [len(w) for w in group_uhgs] + [len(w) for w in river_uhgs])
+    max_len = width if max_len is None else int(max_len)  # a smaller max_len than the tables' width: a refusal test
+    gw = np.zeros((G, width))
+    for k, w in enumerate(group_uhgs):
+        gw[k, :len(w)] = w
+    rw = np.zeros((R, width))
+    for k, w in enumerate(river_uhgs):
+        rw[k, :len(w)] = w
+    glen = np.array([len(w) for w in group_uhgs], dtype=np.int32)
+    rlen = np.array([len(w) for w in river_uhgs], dtype=np.int32)
+    gr = np.ascontiguousarray(group_river, dtype=np.int32)
+    rd = np.ascontiguousarray(river_downstream, dtype=np.int32)
+    if sums_dev_ptr is None:
+        s = np.ascontiguousarray(group_sums, dtype=np.float64)
+        assert s.ndim == 2 and s.shape[0] == G
+        T = s.shape[1]
+        src, on_dev = _ptr(s), 0
+    else:
+        assert not host
+        src, on_dev = C.c_void_p(sums_dev_ptr), 1
+    out = [np.zeros((P, R, T)) for _ in range(3)]
+    if host:
+        check(L.shyft_hip_route_members_host(P, _ptr(row), T, src, _ptr(gw), _ptr(glen), _ptr(gr), R, _ptr(rw),
+                                             _ptr(rlen), _ptr(rd), max_len, _ptr(out[0]), _ptr(out[1]), _ptr(out[2])),
+              None)
+    else:
+        check(L.shyft_hip_route_members(device, P, _ptr(row), T, src, on_dev, _ptr(gw), _ptr(glen), _ptr(gr), R,
+                                        _ptr(rw), _ptr(rlen), _ptr(rd), max_len, _ptr(out[0]), _ptr(out[1]),
+                                        _ptr(out[2]), 0), None)
+    return tuple(out)
+
+
+def route_members_last_ms(device: int = -1) -> float:
+    return float(lib().shyft_hip_route_members_last_ms(device))
 
 
 def btk(src_xyz, src_values, prior_gradient, btk_param, dst_xyz, device: int = -1, block_steps: int = 0) -> np.ndarray:
