@@ -1,8 +1,9 @@
-// Internal: the region handle behind the C ABI (include/shyft_hip.h), shared by region.hip (one region on one
-// device) and shards.hip (a region whose cells are split over several regions / devices).
+// Internal: the region handle behind the C ABI (include/shyft_hip.h), shared by region.hip and the region_*.hip
+// files (one region on one device) and shards.hip (a region whose cells are split over several regions / devices).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -76,8 +77,6 @@ struct shyft_hip_region {
 
     // host mirrors
     std::vector<double> geo;  // n x 11
-    std::vector<int64_t> routing_id;
-    std::vector<double> routing_distance;
     std::vector<int64_t> cid;          // per cell
     std::vector<size_t> cix;           // per cell
     std::vector<int64_t> cix_to_cid;   // region_model::cix_to_cid
@@ -147,7 +146,7 @@ struct shyft_hip_region {
     shyft_hip_region* ens = nullptr;
     const shyft_hip_region* forcing_src = nullptr;  // set on an ensemble lane region: whose forcing it reads
     dbuf<int32_t> d_fcol;                            // [lanes] forcing column (cell of the parent region)
-    size_t ens_members = 0, ens_cells = 0, ens_groups = 0, ens_b = 0, ens_e = 0;
+    size_t ens_members = 0, ens_groups = 0, ens_b = 0, ens_e = 0;
     std::vector<int32_t> ens_k_of_cell;  // [n] the cell's rank among the calculated cells of the last ensemble run, -1 = none
     dbuf<double> d_ens_scratch;          // shyft_hip_ensemble_scratch: the caller's device rows between two ensemble entries
 
@@ -181,6 +180,39 @@ inline int guarded(shyft_hip_region* h, F&& f) {
     } catch (...) {
         return fail(h, "unknown error");
     }
+}
+
+// ---- helpers of the region entries, defined in region.hip and shared by the region_*.hip files
+hipError_t region_copy(shyft_hip_region* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+void copy_rows(hipStream_t s, double* dst, const double* src, size_t bytes, int dst_dev, int src_dev);
+void check_window(const shyft_hip_region* h, size_t step0, size_t n, const char* what);
+double* series_rows(const shyft_hip_region* h, int series, size_t step0, size_t n, const char* what);
+std::vector<int32_t> select_cells(const shyft_hip_region* h, const int64_t* ids, size_t n_ids, int scope);
+void update_derived(shyft_hip_region* h);
+void launch_run(shyft_hip_region* h, int start_step, int n_steps);
+void finish_run(shyft_hip_region* h);
+double btk_prior_gradient(int64_t start_us, int64_t dt_us);
+
+template <class T>
+void clone_buf(dbuf<T>& dst, const dbuf<T>& src) {
+    dst.release();
+    if (!src.p) return;
+    dst.alloc(src.n);
+    hip_check(hipMemcpy(dst.p, src.p, src.n * sizeof(T), hipMemcpyDeviceToDevice), "clone");
+}
+
+// A result of `count` doubles for `dst`: launch(out) writes them to the device, to dst itself when that is on the
+// device and else to h->d_tmp, grown to hold them. They are then copied to the host, or h's stream is waited for.
+template <class F>
+void staged_rows(shyft_hip_region* h, double* dst, size_t count, int dst_on_device, F&& launch) {
+    double* out = dst;
+    if (!dst_on_device) {
+        h->d_tmp.alloc(std::max(h->d_tmp.n, count));
+        out = h->d_tmp.p;
+    }
+    launch(out);
+    if (!dst_on_device) copy_rows(h->stream, dst, out, count * sizeof(double), 0, 1);
+    else hip_check(hipStreamSynchronize(h->stream), "sync");
 }
 
 }  // namespace shyft_hip_impl

@@ -1,4 +1,4 @@
-// Internal: the sharded-region layer (shards.hip) behind the C ABI entry points of region.hip.
+// Internal: the sharded-region layer (shards.hip) behind the C ABI entry points of region.hip and region_*.hip.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -14,7 +14,7 @@ void shard_set_destroy(shard_set* s);
 // region.hip: the generator keys of a region's cells (null: 0..n-1), for a z-balanced shard
 void region_set_cell_ids(shyft_hip_region* h, const int64_t* ids);  // throws
 
-// region.hip: sum over the selected cells of one region (select_cells semantics), value x cell area when weighted;
+// region_series.hip: sum over the selected cells of one region (select_cells semantics), value x cell area when weighted;
 // *sum_area = the selected cells' area sum (weighted only). dst[n] host. No selection match: dst = 0.
 int region_selected_sums(shyft_hip_region* h, int series, const int64_t* ids, size_t n_ids, int scope, int weighted,
                          size_t step0, size_t n, double* dst, double* sum_area, size_t* n_selected);

@@ -37,6 +37,7 @@
 
 #include "../../../include/shyft_hip.h"
 #include "../include_internal/device_call.h"
+#include "../include_internal/host_tables.h"
 
 using namespace shyft_hip_impl;
 
@@ -141,12 +142,7 @@ __global__ __launch_bounds__(RM_TILE) void rm_out_kernel(const rm_args a, int le
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-struct rm_tables {
-    std::vector<int64_t> pair_off;     // [P*R + 1]
-    std::vector<int32_t> pair_groups;  // [G]
-    std::vector<int32_t> up_off, ups;  // upstream CSR
-    std::vector<int32_t> lvl_off, lvl_rivers;
-};
+using rm_tables = river_tables<int64_t>;
 
 // The argument checks shared by the device entry and its host twin, before the device is touched; builds the tables.
 // Returns false when there is nothing to do.
@@ -176,54 +172,8 @@ bool rm_check(size_t P, const int64_t* group_row, size_t T, const double* group_
         if (river_downstream[r] < -1 || river_downstream[r] >= int32_t(R) || river_downstream[r] == int32_t(r))
             throw std::runtime_error("route_members: invalid downstream river");
     }
-    // groups of each (member, river), ascending row
-    tb.pair_off.assign(P * R + 1, 0);
-    tb.pair_groups.resize(G);
-    for (size_t m = 0; m < P; ++m)
-        for (int64_t g = group_row[m]; g < group_row[m + 1]; ++g) tb.pair_off[m * R + size_t(group_river[g]) + 1]++;
-    for (size_t k = 0; k < P * R; ++k) tb.pair_off[k + 1] += tb.pair_off[k];
-    {
-        std::vector<int64_t> pos(tb.pair_off.begin(), tb.pair_off.end() - 1);
-        for (size_t m = 0; m < P; ++m)
-            for (int64_t g = group_row[m]; g < group_row[m + 1]; ++g)
-                tb.pair_groups[size_t(pos[m * R + size_t(group_river[g])]++)] = int32_t(g);
-    }
-    // upstream rivers, ascending index (= ascending id)
-    tb.up_off.assign(R + 1, 0);
-    tb.ups.clear();
-    for (size_t r = 0; r < R; ++r) {
-        for (size_t u = 0; u < R; ++u)
-            if (river_downstream[u] == int32_t(r)) tb.ups.push_back(int32_t(u));
-        tb.up_off[r + 1] = int32_t(tb.ups.size());
-    }
-    // network levels: level(r) = 1 + max level of its upstream rivers (sources are level 0)
-    std::vector<int32_t> level(R, -1);
-    for (size_t pass = 0; pass <= R; ++pass) {
-        bool changed = false;
-        for (size_t r = 0; r < R; ++r) {
-            int32_t lv = 0;
-            bool ready = true;
-            for (int32_t k = tb.up_off[r]; k < tb.up_off[r + 1]; ++k) {
-                const int32_t ul = level[size_t(tb.ups[size_t(k)])];
-                if (ul < 0) { ready = false; break; }
-                lv = std::max(lv, ul + 1);
-            }
-            if (ready && level[r] != lv) { level[r] = lv; changed = true; }
-        }
-        if (!changed) break;
-    }
-    int32_t n_levels = 0;
-    for (size_t r = 0; r < R; ++r) {
-        if (level[r] < 0) throw std::runtime_error("route_members: the river network has a cycle");
-        n_levels = std::max(n_levels, level[r] + 1);
-    }
-    tb.lvl_off.assign(size_t(n_levels) + 1, 0);
-    tb.lvl_rivers.clear();
-    for (int32_t l = 0; l < n_levels; ++l) {
-        for (size_t r = 0; r < R; ++r)
-            if (level[r] == l) tb.lvl_rivers.push_back(int32_t(r));
-        tb.lvl_off[size_t(l) + 1] = int32_t(tb.lvl_rivers.size());
-    }
+    if (!build_river_tables(P, group_row, group_river, R, river_downstream, tb))
+        throw std::runtime_error("route_members: the river network has a cycle");
     return true;
 }
 

@@ -138,14 +138,20 @@ hipError_t launch_select_sum(const double* series, size_t n_cells, size_t n_step
 
 hipError_t launch_segment_sums(const double* series, size_t n_cells, size_t n_steps, const int32_t* seg_cells,
                                const int32_t* seg_off, size_t n_seg, double* out, hipStream_t stream, const double* w) {
-    if (n_steps == 0 || n_seg == 0) return hipSuccess;
-    const dim3 grid((unsigned)n_steps, (unsigned)n_seg);
-    if (!seg_cells) {
-        if (w) hipLaunchKernelGGL((segment_sum_kernel<true, true>), grid, dim3(RB), 0, stream, series, n_cells, n_steps, seg_cells, seg_off, out, w);
-        else hipLaunchKernelGGL((segment_sum_kernel<true, false>), grid, dim3(RB), 0, stream, series, n_cells, n_steps, seg_cells, seg_off, out, w);
-    } else {
-        if (w) hipLaunchKernelGGL((segment_sum_kernel<false, true>), grid, dim3(RB), 0, stream, series, n_cells, n_steps, seg_cells, seg_off, out, w);
-        else hipLaunchKernelGGL((segment_sum_kernel<false, false>), grid, dim3(RB), 0, stream, series, n_cells, n_steps, seg_cells, seg_off, out, w);
+    if (n_steps == 0) return hipSuccess;
+    // the segments go in grid.y, a slice of them per launch: a slice's kernel sees its own seg_off and out rows
+    constexpr size_t SLICE = 65535;
+    for (size_t s0 = 0; s0 < n_seg; s0 += SLICE) {
+        const dim3 grid((unsigned)n_steps, (unsigned)std::min(SLICE, n_seg - s0));
+        const int32_t* off = seg_off + s0;
+        double* o = out + s0 * n_steps;
+        if (!seg_cells) {
+            if (w) hipLaunchKernelGGL((segment_sum_kernel<true, true>), grid, dim3(RB), 0, stream, series, n_cells, n_steps, seg_cells, off, o, w);
+            else hipLaunchKernelGGL((segment_sum_kernel<true, false>), grid, dim3(RB), 0, stream, series, n_cells, n_steps, seg_cells, off, o, w);
+        } else {
+            if (w) hipLaunchKernelGGL((segment_sum_kernel<false, true>), grid, dim3(RB), 0, stream, series, n_cells, n_steps, seg_cells, off, o, w);
+            else hipLaunchKernelGGL((segment_sum_kernel<false, false>), grid, dim3(RB), 0, stream, series, n_cells, n_steps, seg_cells, off, o, w);
+        }
     }
     return hipGetLastError();
 }

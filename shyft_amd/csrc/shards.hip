@@ -7,7 +7,7 @@
 // data-path exchange; the only cross-shard step is the combination of per-catchment / per-routing-group partial
 // sums:
 //   - every shard reduces its cells into [rows][steps] partials on its device (the deterministic segment sums of
-//     region.hip), scattered to the region's global row order;
+//     region_series.hip and region_routing.hip), scattered to the region's global row order;
 //   - the partials are all-gathered: RCCL ncclAllGather over xGMI when every shard has its own device (one
 //     communicator per device from ncclCommInitAll), device-to-device copies when shards share a device;
 //   - each device adds the gathered partials in shard order (fixed order: deterministic, and bit-equal to the

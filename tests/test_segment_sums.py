@@ -58,3 +58,30 @@ def test_routing_group_sums_bit_exact_in_device_order(region):
     r.set_routing_groups(groups, 4)
     got = r.routing_group_sums(0, series.shape[0])
     assert np.array_equal(got, expected(series, groups, [0, 1, 2, 3]))
+
+
+@pytest.mark.parametrize("layout", ["interleaved", "identity"])
+def test_more_catchments_than_one_launch_takes(layout):
+    """65,537 catchments of two cells each: the segments go in grid.y, 65,535 of them per launch (kernels/stats.hip), so
+    the last two catchments are the second launch's, with its own offsets and output rows. Interleaved (catchment
+    i % C: the index array is read) and identity (catchment i // 2: it is not). Two addends sum the same in either
+    order, so the sums are exact."""
+    from shyft_amd.region import HipRegion, PT_GS_K, SERIES_FORCING
+    C, T, var = 65_537, 2, 1
+    n = 2 * C
+    cid = np.arange(n) % C if layout == "interleaved" else np.arange(n) // 2
+    geo = synthetic.geo11(n, n_catchments=3)
+    geo[:, 4] = cid
+    v = np.random.default_rng(11).standard_normal((T, n)) * np.exp2(np.arange(n) % 40)   # differs per cell and step
+    r = HipRegion(PT_GS_K, n)
+    try:
+        r.set_geo(geo)
+        r.set_time_axis(synthetic.T0_2015_US, synthetic.HOUR_US, T)
+        r.set_forcing(var, 0, v)
+        assert np.array_equal(r.catchment_ids(), np.arange(C))
+        got = r.catchment_sums(SERIES_FORCING + var, 0, T)
+    finally:
+        r.close()
+    want = v[:, :C] + v[:, C:] if layout == "interleaved" else v[:, 0::2] + v[:, 1::2]
+    assert got.shape == (C, T)
+    assert np.array_equal(got, want.T)

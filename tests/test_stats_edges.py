@@ -508,10 +508,9 @@ def test_forcing_ok_sees_every_element_and_only_active_cells():
 
 @pytest.mark.gpu
 def test_seventy_thousand_routing_groups():
-    """70,000 groups of one cell each (a few empty): the segment count is the launch's grid.y. The MI355X reports
-    maxGridSize[1] = 65,536, but the runtime takes the launch of 70,000 and every segment, those at and above 65,536
-    included, gets its sum: launch_segment_sums needs no slices today. Should a runtime begin to refuse such a launch,
-    this test fails with its error return, and slicing by offsetting seg_off and out is the remedy."""
+    """70,000 groups of one cell each (a few empty): the segments go in the launch's grid.y, and the MI355X reports
+    maxGridSize[1] = 65,536. launch_segment_sums launches them in slices of 65,535, each with its own seg_off and out
+    rows: every segment, those next to the slice boundary and above it included, gets its sum."""
     from shyft_amd.region import COLLECT_DISCHARGE
     n, T = 70_000, 2
     r = new_region(n, T, synthetic.geo11(n, n_catchments=3), COLLECT_DISCHARGE)
