@@ -1,10 +1,9 @@
-// What a percentile entry reads of a sorted sample set, and the order-preserving 64-bit key of an fp64 sample. Shared
-// by kernels/percentiles.hip (the cells of a region), kernels/ts_percentiles.hip (a vector of series) and, for the
-// plan alone, host/ts_percentiles.hpp; there is one copy.
+// What a percentile entry reads of a sorted sample set. Shared by kernels/percentiles.hip (the cells of a region),
+// kernels/ts_percentiles.hip (a vector of series) and, for the plan alone, host/ts_percentiles.hpp; there is one copy.
+// The order-preserving key of an fp64 sample is device-only and lives in device/workgroup.h.
 //
-// The plan is plain C++ and compiles for the host and the device; the key functions and pct_value are device code and
-// exist only under hipcc. pct_value's multiply and add are rounded separately (-ffp-contract=off on every file that
-// includes this).
+// The plan is plain C++ and compiles for the host and the device; pct_value is device code and exists only under
+// hipcc. Its multiply and add are rounded separately (-ffp-contract=off on every file that includes this).
 #pragma once
 #include <stdint.h>
 
@@ -58,20 +57,6 @@ PCT_HD inline pct_plan pct_make_plan(int64_t p, int ns) {
 }
 
 #ifdef __HIPCC__
-constexpr uint64_t PCT_SIGN = 0x8000000000000000ull;
-constexpr uint64_t PCT_EXPO = 0x7ff0000000000000ull;
-
-__device__ inline bool key_of(double v, uint64_t& key) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    key = (u & PCT_SIGN) ? ~u : (u | PCT_SIGN);
-    return (u & PCT_EXPO) != PCT_EXPO;  // finite
-}
-__device__ inline double value_of(uint64_t key) {
-    const uint64_t u = (key & PCT_SIGN) ? (key ^ PCT_SIGN) : ~key;
-    return __longlong_as_double((long long)u);
-}
-__device__ inline double pct_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
 __device__ inline double pct_value(const pct_plan& pl, double lower, double upper) {
     if (pl.kind == PCT_SINGLE) return lower;
     return lower + pl.delta * (upper - lower);  // separately rounded multiply and add (-ffp-contract=off)

@@ -4,7 +4,7 @@
 // per interval of a shifted view); there is one copy.
 //
 // Every operation is evaluated as written: int64 tick arithmetic, to_seconds(x) = double(x) / 1e6 as a division,
-// no FMA (-ffp-contract=off), isfinite by the exponent bits.
+// no FMA (-ffp-contract=off), isfinite by the exponent bits (rs_nan and rs_finite: device/workgroup.h).
 //
 // Index safety. The caller passes the n > 0 points of one series, whose times increase strictly and whose t_end lies
 // after the last (checked on the host before the launch). rs_area reads point k only with k < n: the start index is
@@ -16,10 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-constexpr uint64_t RS_EXPO = 0x7ff0000000000000ull;
+#include "workgroup.h"
 
-__device__ inline double rs_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ inline bool rs_finite(double x) { return ((uint64_t)__double_as_longlong(x) & RS_EXPO) != RS_EXPO; }
 __device__ inline double rs_seconds(int64_t dt) { return double(dt) / 1e6; }
 __device__ inline int64_t rs_max(int64_t a, int64_t b) { return a > b ? a : b; }
 __device__ inline int64_t rs_min(int64_t a, int64_t b) { return a < b ? a : b; }
@@ -49,13 +47,7 @@ __device__ inline double rs_area(const int64_t* __restrict__ t_stored, const dou
     } else if (ps >= t[n - 1]) {
         i = n - 1;
     } else {  // upper_bound - 1; t[0] <= ps < t[n-1]
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t m = lo + ((hi - lo) >> 1);
-            if (t[m] <= ps) lo = m + 1;
-            else hi = m;
-        }
-        i = lo - 1;
+        i = first_false(int64_t(0), n, [&](int64_t m) { return t[m] <= ps; }) - 1;
     }
     int64_t lt = 0;
     double lv = rs_nan();

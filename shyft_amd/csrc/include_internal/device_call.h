@@ -2,6 +2,7 @@
 // shyft_hip_ts_* entries, _forecast_skill, shyft_hip_btk, shyft_hip_ordinary_kriging) share on the host side of one device call.
 #pragma once
 #include <atomic>
+#include <string>
 
 #include "region_impl.h"
 
@@ -69,6 +70,35 @@ struct per_device {
     T load(int device, T fallback) const {
         if (device < 0 && hipGetDevice(&device) != hipSuccess) return fallback;
         return in_range(device) ? v[device].load() : fallback;
+    }
+};
+
+// The grid of a kernel whose stride loop takes what the grid does not: at least one block, at most 2^20.
+inline unsigned launch_blocks(size_t blocks) {
+    const size_t max_grid = size_t(1) << 20;
+    return unsigned(blocks < max_grid ? (blocks ? blocks : 1) : max_grid);
+}
+
+// What the getters of one entry family report per device: the kernel milliseconds of the last call, the calls so far
+// and the last launch shape. A family without a shape or a call getter leaves that member unread.
+struct call_record {
+    static constexpr int KEEP_PATH = -0x7fffffff - 1;
+    per_device<double> last_ms;
+    per_device<uint64_t> calls;
+    per_device<int> last_path;
+    // the counters alone, for an entry that downloads several arrays or adds up the times of several launches
+    void record(int dev, double ms, int path = KEEP_PATH) {
+        last_ms.store(dev, ms);
+        calls.fetch_add(dev, 1);
+        if (path != KEEP_PATH) last_path.store(dev, path);
+    }
+    // after the last launch of a timed call with one result array: the end of the timed part, the result, the wait,
+    // and the counters
+    template <class T>
+    void finish(device_call& c, const char* what, T* out, const T* d_out, size_t count, int path = KEEP_PATH) {
+        c.end();
+        c.download(out, d_out, count, (std::string(what) + " download").c_str());
+        record(c.dev, c.finish(what), path);
     }
 };
 

@@ -215,8 +215,7 @@ void fs_fill_nan(double* x, size_t count) {
     if (x) std::fill(x, x + count, std::numeric_limits<double>::quiet_NaN());
 }
 
-per_device<double> g_fs_last_ms;
-per_device<uint64_t> g_fs_calls;
+call_record g_fs;
 constexpr const char* FS_UPLOAD = "forecast_skill upload";
 
 }  // namespace
@@ -272,18 +271,14 @@ int shyft_hip_forecast_skill(int device, size_t S, const int64_t* row, const int
         a.ns = d_ns.p;
         a.sim = d_sim.p;
         a.obs = d_obs.p;
-        const size_t max_grid = size_t(1) << 20;  // the grid-stride loop takes the rest
-        const size_t blocks = (P + FS_WAVES - 1) / FS_WAVES;
         c.begin();
-        hipLaunchKernelGGL(forecast_skill_kernel, dim3(unsigned(blocks < max_grid ? blocks : max_grid)), dim3(FS_BLOCK), 0,
-                           c.s, a);
+        hipLaunchKernelGGL(forecast_skill_kernel, dim3(launch_blocks((P + FS_WAVES - 1) / FS_WAVES)), dim3(FS_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "forecast_skill");
         c.end();
         if (ns) c.download(ns, d_ns.p, P, "forecast_skill download");
         if (sim) c.download(sim, d_sim.p, J, "forecast_skill download");
         if (obs) c.download(obs, d_obs.p, J, "forecast_skill download");
-        g_fs_last_ms.store(c.dev, c.finish("forecast_skill"));
-        g_fs_calls.fetch_add(c.dev, 1);
+        g_fs.record(c.dev, c.finish("forecast_skill"));
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -326,8 +321,8 @@ int shyft_hip_forecast_skill_host(int device, size_t S, const int64_t* row, cons
     }
 }
 
-double shyft_hip_forecast_skill_last_ms(int device) { return g_fs_last_ms.load(device, 0.0); }
+double shyft_hip_forecast_skill_last_ms(int device) { return g_fs.last_ms.load(device, 0.0); }
 
-uint64_t shyft_hip_forecast_skill_calls(int device) { return g_fs_calls.load(device, 0); }
+uint64_t shyft_hip_forecast_skill_calls(int device) { return g_fs.calls.load(device, 0); }
 
 }  // extern "C"

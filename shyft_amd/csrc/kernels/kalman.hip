@@ -253,7 +253,7 @@ bool kalman_prepare(const char* who, int n, size_t M, size_t T, const double* bi
     return false;
 }
 
-per_device<double> g_kalman_last_ms;
+call_record g_kalman;
 constexpr const char* KALMAN_UPLOAD = "kalman upload";
 constexpr const char* KALMAN_DOWNLOAD = "kalman download";
 
@@ -312,7 +312,7 @@ int shyft_hip_kalman_run(int device, int n, size_t M, size_t T, const double* bi
         c.download(k, d_k.p, size_t(n) * M, KALMAN_DOWNLOAD);
         c.download(P, d_P.p, nn * M, KALMAN_DOWNLOAD);
         if (out) c.download(out, d_out.p, T * M, KALMAN_DOWNLOAD);
-        g_kalman_last_ms.store(c.dev, c.finish("kalman_run"));
+        g_kalman.record(c.dev, c.finish("kalman_run"));
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -364,6 +364,6 @@ int shyft_hip_kalman_initial_state(int n, double covariance_init, double hourly_
     return 0;
 }
 
-double shyft_hip_kalman_last_ms(int device) { return g_kalman_last_ms.load(device, 0.0); }
+double shyft_hip_kalman_last_ms(int device) { return g_kalman.last_ms.load(device, 0.0); }
 
 }  // extern "C"

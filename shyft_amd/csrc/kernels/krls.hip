@@ -10,7 +10,7 @@
 //   Kinv q for those rows, one accumulator each, adding the terms in index order as the host does, and it updates
 //   those rows. For a' P the same lane owns the COLUMNS l, l + KRLS_BLOCK, ... and walks down them. The four scalar
 //   products (k.a, k.alpha, a.Pa, and the f(x) of the running mse) are krls_dot of host/krls.hpp: every wavefront
-//   forms the same 64 strided partial sums and folds them with six xor exchanges, so all lanes of the workgroup hold
+//   forms the same 64 strided partial sums and folds them with six xor exchanges (wave_reduce, device/workgroup.h), so all lanes of the workgroup hold
 //   the same bits and the grow/update decision delta > tolerance is uniform without a broadcast.
 //   Layout. k, a, Pa, r, q, alpha and d live in LDS, `cap` doubles each. The matrices are row-major with the leading
 //   dimension ld = cap | 1, an odd count of doubles. ds_read_b64 serves 32 lanes per cycle from 64 four-byte banks,
@@ -59,6 +59,7 @@
 #include <vector>
 
 #include "../../../include/shyft_hip.h"
+#include "../device/workgroup.h"
 #include "../host/krls.hpp"
 #include "../include_internal/device_call.h"
 #include "../include_internal/series_args.h"
@@ -116,9 +117,7 @@ struct krls_train_args {
 __device__ inline double krls_wave_dot(const double* u, const double* v, int m, int lane) {
     double acc = 0.0;
     for (int i = lane; i < m; i += 64) acc = acc + u[i] * v[i];
-#pragma unroll
-    for (int o = 32; o >= 1; o /= 2) acc = acc + __shfl_xor(acc, o, 64);
-    return acc;
+    return wave_reduce(acc, op_add());
 }
 
 template <bool IN_LDS>
@@ -439,7 +438,7 @@ void krls_train_on_host(const krls_in& in, size_t s, shyft_hip_krls_result& R) {
     R.path[s] = SHYFT_HIP_KRLS_PATH_HOST;
 }
 
-per_device<double> g_krls_last_ms;
+call_record g_krls;
 std::atomic<int> g_krls_path{0};  // shyft_hip_krls_set_path
 constexpr const char* KRLS_UPLOAD = "krls upload";
 constexpr const char* KRLS_DOWNLOAD = "krls download";
@@ -637,7 +636,7 @@ int shyft_hip_krls_train_csr(int device, size_t S, const int64_t* row, const int
                 }
                 pending.swap(later);
             }
-            g_krls_last_ms.store(c.dev, ms);
+            g_krls.record(c.dev, ms);
         }
         host_round.insert(host_round.end(), pending.begin(), pending.end());  // beyond KRLS_MAX_DICT
         for (size_t s : host_round) krls_train_on_host(in, s, *R);
@@ -727,13 +726,12 @@ int shyft_hip_krls_predict(int device, size_t S, const int64_t* d_row, const dou
         d_out.alloc(nq);
         krls_predict_args a{int64_t(ntiles), d_tile_s.p, d_tile_i0.p, d_drow.p, d_d.p, d_alpha.p, d_scaling.p, d_gamma.p,
                             d_qrow.p, d_qt.p, q_v ? d_qv.p : nullptr, d_out.p};
-        const size_t max_grid = size_t(1) << 20;  // the tile loop takes the rest
         c.begin();
-        hipLaunchKernelGGL(krls_predict_k, dim3(unsigned(ntiles < max_grid ? ntiles : max_grid)), dim3(KRLS_BLOCK), 0, c.s, a);
+        hipLaunchKernelGGL(krls_predict_k, dim3(launch_blocks(ntiles)), dim3(KRLS_BLOCK), 0, c.s, a);  // the tile loop takes the rest
         hip_check(hipGetLastError(), "krls_predict");
         c.end();
         c.download(out, d_out.p, nq, KRLS_DOWNLOAD);
-        g_krls_last_ms.store(c.dev, c.finish("krls_predict"));
+        g_krls.record(c.dev, c.finish("krls_predict"));
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -761,7 +759,7 @@ int shyft_hip_krls_predict_host(int device, size_t S, const int64_t* d_row, cons
     }
 }
 
-double shyft_hip_krls_last_ms(int device) { return g_krls_last_ms.load(device, 0.0); }
+double shyft_hip_krls_last_ms(int device) { return g_krls.last_ms.load(device, 0.0); }
 
 int shyft_hip_krls_set_path(int path) {
     if (path != 0 && path != SHYFT_HIP_KRLS_PATH_WORKSPACE) return fail(nullptr, "krls: path must be 0 or SHYFT_HIP_KRLS_PATH_WORKSPACE");

@@ -17,12 +17,14 @@
 //    host round trip per step or per pass.
 //  - AVERAGE: the finite samples summed by lanes striding in cell order, then the fixed wavefront shuffle tree + LDS
 //    combine of kernels/stats.hip, divided by the finite count: reproducible run to run, and the same for both
-//    paths (it is not the reference's sorted sequential sum, time_series_statistics.h:127-132).
+//    paths (it is not the reference's sorted sequential sum, time_series_statistics.h:127-132). The combine is
+//    block_sum of device/workgroup.h, the one kernels/stats.hip calls.
 //  - No floating-point atomics anywhere.
 //
 // Index safety: cell indexes come from select_cells / the region's segment tables (< n_cells); a digit is key bits
-// masked to 0..255; histogram rows are indexed by a selection number < 2 * n_pct; the LDS sort reads rank
-// min(rank, nf - 1) of a power-of-two array of at least nf keys; a job without finite samples writes NaNs only.
+// masked to 0..255; histogram rows are indexed by a selection number < 2 * n_pct; the LDS sort pads and sorts slots
+// below Q <= P (device/workgroup.h states its own reads) and reads rank min(rank, nf - 1) of the at least nf keys; a
+// job without finite samples writes NaNs only.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -31,6 +33,7 @@
 #include <vector>
 
 #include "../device/pct_plan.h"
+#include "../device/workgroup.h"
 #include "../include_internal/kernels.h"
 
 namespace {
@@ -40,18 +43,10 @@ constexpr int PCT_MAX = SHYFT_HIP_PERCENTILES_MAX;
 constexpr int PCT_SEL = 2 * PCT_MAX;    // selections (ranks) per job: lower and upper of every percentile
 constexpr int PCT_CHUNK = 16384;        // cells of a job's row per histogram workgroup
 
-// pct_plan / pct_make_plan, key_of / value_of and pct_value: device/pct_plan.h, shared with kernels/ts_percentiles.hip
+// pct_plan / pct_make_plan and pct_value: device/pct_plan.h, shared with kernels/ts_percentiles.hip; key_of / value_of,
+// the workgroup sum and scan and the LDS sort: device/workgroup.h
 
 // ---------------------------------------------------------------------------------------------- AVERAGE
-__device__ inline double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ inline uint32_t wave_sum_u(uint32_t v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // One workgroup per job (blockIdx.x = seg * n_steps + t). Lane l adds the finite ones of the segment's elements
 // l, l + 256, ... in that order (four loads ahead, added in the same order).
 template <bool ID>
@@ -59,8 +54,6 @@ __global__ __launch_bounds__(PB) void pct_average_kernel(const double* __restric
                                                          const int32_t* __restrict__ seg_cells,
                                                          const int32_t* __restrict__ seg_off, pct_list pl,
                                                          double* __restrict__ out) {
-    __shared__ double part[PB / 64];
-    __shared__ uint32_t cpart[PB / 64];
     const int job = blockIdx.x;
     const int c = job / n_steps, t = job - c * n_steps;
     const double* __restrict__ row = series + (size_t)t * n_cells;
@@ -89,22 +82,10 @@ __global__ __launch_bounds__(PB) void pct_average_kernel(const double* __restric
             ++cnt;
         }
     }
-    acc = wave_sum(acc);
-    cnt = wave_sum_u(cnt);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) {
-        part[wid] = acc;
-        cpart[wid] = cnt;
-    }
-    __syncthreads();
+    const double s = block_sum<PB>(acc);
+    const uint32_t n = block_sum<PB>(cnt);
     if (threadIdx.x == 0) {
-        double s = part[0];
-        uint32_t n = cpart[0];
-        for (int w = 1; w < PB / 64; ++w) {
-            s += part[w];
-            n += cpart[w];
-        }
-        const double r = n > 0 ? s / double(n) : pct_nan();
+        const double r = n > 0 ? s / double(n) : rs_nan();
         for (int i = 0; i < pl.n; ++i)
             if (pl.p[i] == -1) out[((size_t)c * pl.n + i) * n_steps + t] = r;
     }
@@ -135,30 +116,13 @@ __global__ __launch_bounds__(PB) void pct_lds_sort_kernel(const double* __restri
     }
     __syncthreads();
     const int nf = (int)n_fin;
-    int Q = 1;  // power of two >= nf, <= P
-    while (Q < nf) Q <<= 1;
-    for (int i = nf + (int)threadIdx.x; i < Q; i += PB) keys[i] = ~0ull;
+    const int Q = lds_sort_pad<false>(keys, nullptr, nf, (int)threadIdx.x, PB);  // power of two >= nf, <= P
     __syncthreads();
-    for (int k = 2; k <= Q; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < Q; i += PB) {
-                const int x = i ^ j;
-                if (x > i) {
-                    const uint64_t a = keys[i], d = keys[x];
-                    const bool up = (i & k) == 0;
-                    if ((a > d) == up) {
-                        keys[i] = d;
-                        keys[x] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    lds_bitonic_sort<false, false>(keys, nullptr, Q, (int)threadIdx.x, PB);
     for (int i = threadIdx.x; i < pl.n; i += PB) {
         const pct_plan q = pct_make_plan(pl.p[i], nf);
         if (q.kind == PCT_AVG) continue;  // pct_average_kernel writes these
-        double r = pct_nan();
+        double r = rs_nan();
         if (q.kind != PCT_NAN) {
             const uint32_t last = uint32_t(nf - 1);
             r = pct_value(q, value_of(keys[q.lo < last ? q.lo : last]), value_of(keys[q.hi < last ? q.hi : last]));
@@ -250,25 +214,7 @@ __global__ __launch_bounds__(PB) void pct_hist_kernel(const double* __restrict__
     }
 }
 
-// exclusive prefix sum of one value per lane over the 256 lanes of the workgroup; *total = the sum
-__device__ inline uint32_t block_scan_excl(uint32_t v, uint32_t* wtot, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    __syncthreads();  // wtot of the previous scan has been read
-    if (lane == 63) wtot[wid] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-    for (int w = 0; w < PB / 64; ++w) {
-        if (w < wid) base += wtot[w];
-        tot += wtot[w];
-    }
-    *total = tot;
-    return base + inc - v;
-}
+static_assert(PB == SCAN_BLOCK, "block_scan takes a workgroup of PB lanes");
 
 // One workgroup per job, one lane per digit value. Pass 0: the finite count, the plan of every percentile, the distinct
 // ranks; every pass: the digit bucket each rank falls in. The histogram rows are zeroed for the next pass.
@@ -283,7 +229,7 @@ __global__ __launch_bounds__(PB) void pct_pick_kernel(int pass, int rows, pct_li
         const uint32_t n = g[d];
         g[d] = 0u;
         uint32_t total;
-        const uint32_t ex = block_scan_excl(n, wtot, &total);
+        const uint32_t ex = block_scan(n, op_add(), 0u, wtot, total) - n;  // exclusive
         if (threadIdx.x == 0) {
             js.nf = total;
             int n_u = 0;
@@ -333,7 +279,7 @@ __global__ __launch_bounds__(PB) void pct_pick_kernel(int pass, int rows, pct_li
         uint32_t rank = jobs[jb].urank[u];  // every lane reads before the scan's barriers, one writes after them
         const uint64_t prefix = jobs[jb].uprefix[u];
         uint32_t total;
-        const uint32_t ex = block_scan_excl(n, wtot, &total);
+        const uint32_t ex = block_scan(n, op_add(), 0u, wtot, total) - n;  // exclusive
         if (total > 0u && rank >= total) rank = total - 1u;  // never: the rank lies inside its bucket
         if (n > 0u && ex <= rank && rank - ex < n) {
             jobs[jb].urank[u] = rank - ex;
@@ -353,7 +299,7 @@ __global__ __launch_bounds__(PB) void pct_finish_kernel(int job0, int n_jobs, in
     const uint32_t nf = jobs[jb].nf;
     const pct_plan q = pct_make_plan(pl.p[ip], nf > 0x7fffffffu ? 0x7fffffff : (int)nf);
     if (q.kind == PCT_AVG) return;  // pct_average_kernel writes these
-    double r = pct_nan();
+    double r = rs_nan();
     if (q.kind != PCT_NAN) {
         int lu = jobs[jb].lo_u[ip], hu = jobs[jb].hi_u[ip];
         lu = lu < 0 ? 0 : (lu >= PCT_SEL ? PCT_SEL - 1 : lu);

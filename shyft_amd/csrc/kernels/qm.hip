@@ -7,7 +7,7 @@
 //
 // Per job (host/qm.hpp map_step is the same arithmetic in plain C++, and the definition of correct):
 //  1. the finite forecasts and the finite scenarios are compacted into LDS as (order key, series index) pairs: the
-//     order-preserving key of kernels/percentiles.hip, -0.0 given the key of +0.0 so that zeros tie;
+//     order-preserving key of device/workgroup.h, -0.0 given the key of +0.0 so that zeros tie;
 //  2. both sets are bitonic-sorted lexicographically by (key, index). The index breaks every tie, so the order is
 //     total and the network's instability cannot show: ties go by ascending series index, as on the host. Values are
 //     read back through the index, never through the key;
@@ -25,7 +25,8 @@
 //
 // Index safety: SF and SP are the powers of two >= F and P, and the LDS arrays have SF and SP slots; the compaction
 // takes at most F <= SF and P <= SP slots; a sort runs over the power of two >= the finite count, which is <= SF or
-// SP, and its padding pairs (key and index all ones) sort last and are never read: only ranks < nf and < np are.
+// SP (lds_sort_pad and lds_bitonic_sort, device/workgroup.h, state their own reads), and its padding pairs (key and
+// index all ones) sort last and are never read: only ranks < nf and < np are.
 // Series indexes in LDS are loop indexes < F or < P. The rank j of a quantile is clamped to nf - 1, and j - 1 is read
 // only when j > 0. A job with no finite forecast copies its row and a job with no finite scenario writes NaNs: neither
 // reaches the prefix arrays.
@@ -39,6 +40,7 @@
 #include <string>
 #include <vector>
 
+#include "../device/workgroup.h"
 #include "../host/qm.hpp"
 #include "../include_internal/device_call.h"
 
@@ -48,8 +50,6 @@ namespace {
 
 constexpr int QM_BLOCK = 256;                 // 4 wavefronts
 constexpr int QM_WAVE_JOBS = QM_BLOCK / 64;   // jobs per workgroup on the WAVE path
-constexpr uint64_t QM_SIGN = 0x8000000000000000ull;
-constexpr uint64_t QM_EXPO = 0x7ff0000000000000ull;
 
 struct qm_args {
     size_t jobs;  // B * T
@@ -70,51 +70,10 @@ __host__ __device__ inline size_t qm_job_bytes(int SF, int SP) {
     return (b + 15) & ~size_t(15);
 }
 
-// the key of kernels/percentiles.hip, zeros merged; false for NaN and +-inf
+// key_of with the zeros merged; false for NaN and +-inf
 __device__ inline bool qm_key_of(double v, uint64_t& key) {
-    uint64_t u = (uint64_t)__double_as_longlong(v);
-    if (u == QM_SIGN) u = 0;  // -0.0 ties with +0.0
-    key = (u & QM_SIGN) ? ~u : (u | QM_SIGN);
-    return (u & QM_EXPO) != QM_EXPO;
-}
-__device__ inline double qm_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-template <bool WAVE>
-__device__ inline void qm_sync() {
-    if (WAVE) {
-        // one wavefront: its LDS operations complete in order; the fences keep the compiler from moving or caching
-        // LDS accesses across the point
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-        __syncthreads();
-    }
-}
-
-// bitonic sort of Q (a power of two) pairs, ascending by (key, idx)
-template <bool WAVE>
-__device__ inline void qm_sort(uint64_t* keys, uint32_t* idx, int Q, int tid, int nt) {
-    for (int k = 2; k <= Q; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < Q; i += nt) {
-                const int x = i ^ j;
-                if (x > i) {
-                    const uint64_t a = keys[i], d = keys[x];
-                    const uint32_t ia = idx[i], id = idx[x];
-                    const bool up = (i & k) == 0;
-                    const bool gt = a > d || (a == d && ia > id);
-                    if (gt == up) {
-                        keys[i] = d;
-                        keys[x] = a;
-                        idx[i] = id;
-                        idx[x] = ia;
-                    }
-                }
-            }
-            qm_sync<WAVE>();
-        }
-    }
+    if ((uint64_t)__double_as_longlong(v) == RS_SIGN) v = 0.0;  // -0.0 ties with +0.0
+    return key_of(v, key);
 }
 
 template <bool WAVE>
@@ -143,7 +102,7 @@ __global__ __launch_bounds__(QM_BLOCK) void qm_kernel(qm_args a) {
 
     if (mode != SHYFT_HIP_QM_PRIOR) {  // uniform over the job
         if (tid == 0) cnt[0] = cnt[1] = 0u;
-        qm_sync<WAVE>();
+        lds_sync<WAVE>();
         for (int i = tid; i < F; i += nt) {
             uint64_t key;
             if (qm_key_of(fc[i], key)) {
@@ -160,7 +119,7 @@ __global__ __launch_bounds__(QM_BLOCK) void qm_kernel(qm_args a) {
                 pidx[pos] = uint32_t(i);
             }
         }
-        qm_sync<WAVE>();
+        lds_sync<WAVE>();
     }
     const int nf = mode != SHYFT_HIP_QM_PRIOR ? int(cnt[0]) : 0;
     if (nf == 0) {  // time_series_qm.h:345-347
@@ -170,29 +129,19 @@ __global__ __launch_bounds__(QM_BLOCK) void qm_kernel(qm_args a) {
     const int np = int(cnt[1]);
     for (int i = tid; i < P; i += nt) {
         uint64_t key;
-        if (!qm_key_of(pri[i], key)) out[i] = qm_nan();
+        if (!qm_key_of(pri[i], key)) out[i] = rs_nan();
     }
     if (np == 0) return;
-    int QF = 1, QP = 1;  // powers of two >= nf, np; <= SF, SP
-    while (QF < nf) QF <<= 1;
-    while (QP < np) QP <<= 1;
-    for (int i = nf + tid; i < QF; i += nt) {
-        fkey[i] = ~0ull;
-        fidx[i] = ~0u;
-    }
-    for (int i = np + tid; i < QP; i += nt) {
-        pkey[i] = ~0ull;
-        pidx[i] = ~0u;
-    }
-    qm_sync<WAVE>();
-    qm_sort<WAVE>(fkey, fidx, QF, tid, nt);
-    qm_sort<WAVE>(pkey, pidx, QP, tid, nt);
+    const int QF = lds_sort_pad<true>(fkey, fidx, nf, tid, nt), QP = lds_sort_pad<true>(pkey, pidx, np, tid, nt);  // <= SF, SP
+    lds_sync<WAVE>();
+    lds_bitonic_sort<WAVE, true>(fkey, fidx, QF, tid, nt);  // ascending by (key, index)
+    lds_bitonic_sort<WAVE, true>(pkey, pidx, QP, tid, nt);
     for (int j = tid; j < nf; j += nt) {
         const uint32_t ix = fidx[j];  // < F
         fval[j] = fc[ix];
         fwid[j] = a.w[ix];
     }
-    qm_sync<WAVE>();
+    lds_sync<WAVE>();
     if (tid == 0) {  // sequential in rank order (wvo_accessor, time_series_qm.h:197-208; :88-98, :146-153)
         double w_sum = 0.0;
         for (int j = 0; j < nf; ++j) w_sum += fwid[j];
@@ -214,28 +163,20 @@ __global__ __launch_bounds__(QM_BLOCK) void qm_kernel(qm_args a) {
             }
         }
     }
-    qm_sync<WAVE>();
+    lds_sync<WAVE>();
     const double q_step = 1.0 / double(np - 1);  // inf for one quantile, q_i NaN then
     const double iw = a.interp_weight[t];
     for (int i = tid; i < np; i += nt) {
         const double q_i = q_step * double(i);
-        int lo = 0, hi = nf;
         double q;
-        if (!a.interpolated) {
-            while (lo < hi) {  // first j with !(cum[j+1] < q_i)
-                const int m = (lo + hi) >> 1;
-                if (fa[m] < q_i) lo = m + 1;
-                else hi = m;
-            }
+        if (!a.interpolated) {  // first j with !(cum[j+1] < q_i)
+            const int lo = first_false(0, nf, [&](int m) { return fa[m] < q_i; });
             q = fval[lo < nf - 1 ? lo : nf - 1];
         } else if (np == 1) {
             q = fval[0];
         } else {
-            while (lo < hi) {  // first j with mid[j] > q_i
-                const int m = (lo + hi) >> 1;
-                if (fa[m] > q_i) hi = m;
-                else lo = m + 1;
-            }
+            // first j with mid[j] > q_i
+            const int lo = first_false(0, nf, [&](int m) { return !(fa[m] > q_i); });
             const int j = lo < nf - 1 ? lo : nf - 1;
             if (j == 0 || (j == nf - 1 && q_i >= fa[j])) {
                 q = fval[j];
@@ -272,8 +213,7 @@ bool qm_prepare(const char* who, size_t B, size_t T, size_t F, size_t P, const d
     return false;
 }
 
-per_device<double> g_qm_last_ms;
-per_device<int> g_qm_last_path;
+call_record g_qm;
 constexpr const char* QM_UPLOAD = "quantile_map upload";
 
 }  // namespace
@@ -326,10 +266,7 @@ int shyft_hip_quantile_map(int device, size_t B, size_t T, size_t F, size_t P, c
             hipLaunchKernelGGL(qm_kernel<false>, dim3(unsigned(a.jobs)), dim3(QM_BLOCK), job_bytes, c.s, a);
         }
         hip_check(hipGetLastError(), "quantile_map");
-        c.end();
-        c.download(out, d_out.p, B * T * P, "quantile_map download");
-        g_qm_last_ms.store(c.dev, c.finish("quantile_map"));
-        g_qm_last_path.store(c.dev, wave ? SHYFT_HIP_QM_PATH_WAVE : SHYFT_HIP_QM_PATH_GROUP);
+        g_qm.finish(c, "quantile_map", out, d_out.p, B * T * P, wave ? SHYFT_HIP_QM_PATH_WAVE : SHYFT_HIP_QM_PATH_GROUP);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -353,8 +290,8 @@ int shyft_hip_quantile_map_host(size_t B, size_t T, size_t F, size_t P, const do
     }
 }
 
-int shyft_hip_quantile_map_last_path(int device) { return g_qm_last_path.load(device, SHYFT_HIP_QM_PATH_NONE); }
+int shyft_hip_quantile_map_last_path(int device) { return g_qm.last_path.load(device, SHYFT_HIP_QM_PATH_NONE); }
 
-double shyft_hip_quantile_map_last_ms(int device) { return g_qm_last_ms.load(device, 0.0); }
+double shyft_hip_quantile_map_last_ms(int device) { return g_qm.last_ms.load(device, 0.0); }
 
 }  // extern "C"

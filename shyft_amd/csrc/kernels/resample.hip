@@ -185,9 +185,7 @@ bool rs_prepare(const char* who, int mode, size_t S, const int64_t* row, const i
     return false;
 }
 
-per_device<double> g_rs_last_ms;
-per_device<uint64_t> g_rs_calls;
-per_device<int> g_rs_last_path;
+call_record g_rs;
 std::atomic<int> g_rs_path{SHYFT_HIP_RESAMPLE_PATH_AUTO};
 constexpr const char* RS_UPLOAD = "resample upload";
 
@@ -225,29 +223,21 @@ int shyft_hip_resample(int device, int mode, size_t S, const int64_t* row, const
         const int knob = g_rs_path.load();
         const bool tiled = knob == SHYFT_HIP_RESAMPLE_PATH_TILED ||
                            (knob == SHYFT_HIP_RESAMPLE_PATH_AUTO && T >= size_t(RS_TILE_T));
-        const size_t max_grid = size_t(1) << 20;  // the grid-stride loops take the rest
         c.begin();
         if (tiled) {
             const size_t tiles = ((S + RS_TILE_S - 1) / RS_TILE_S) * ((T + RS_TILE_T - 1) / RS_TILE_T);
-            hipLaunchKernelGGL(resample_tiled_kernel, dim3(unsigned(tiles < max_grid ? tiles : max_grid)), dim3(RS_BLOCK),
-                               0, c.s, a);
+            hipLaunchKernelGGL(resample_tiled_kernel, dim3(launch_blocks(tiles)), dim3(RS_BLOCK), 0, c.s, a);
         } else {
-            const size_t blocks = (T * S + RS_BLOCK - 1) / RS_BLOCK;
-            hipLaunchKernelGGL(resample_direct_kernel, dim3(unsigned(blocks < max_grid ? blocks : max_grid)),
+            hipLaunchKernelGGL(resample_direct_kernel, dim3(launch_blocks((T * S + RS_BLOCK - 1) / RS_BLOCK)),
                                dim3(RS_BLOCK), 0, c.s, a);
         }
         hip_check(hipGetLastError(), "resample");
         if (mode == SHYFT_HIP_RESAMPLE_ACCUMULATE) {
-            const size_t blocks = (S + RS_BLOCK - 1) / RS_BLOCK;
-            hipLaunchKernelGGL(resample_scan_kernel, dim3(unsigned(blocks < max_grid ? blocks : max_grid)), dim3(RS_BLOCK),
-                               0, c.s, S, T, d_out.p);
+            hipLaunchKernelGGL(resample_scan_kernel, dim3(launch_blocks((S + RS_BLOCK - 1) / RS_BLOCK)), dim3(RS_BLOCK), 0,
+                               c.s, S, T, d_out.p);
             hip_check(hipGetLastError(), "resample scan");
         }
-        c.end();
-        c.download(out, d_out.p, T * S, "resample download");
-        g_rs_last_ms.store(c.dev, c.finish("resample"));
-        g_rs_last_path.store(c.dev, tiled ? SHYFT_HIP_RESAMPLE_PATH_TILED : SHYFT_HIP_RESAMPLE_PATH_DIRECT);
-        g_rs_calls.fetch_add(c.dev, 1);
+        g_rs.finish(c, "resample", out, d_out.p, T * S, tiled ? SHYFT_HIP_RESAMPLE_PATH_TILED : SHYFT_HIP_RESAMPLE_PATH_DIRECT);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -304,11 +294,11 @@ int shyft_hip_resample_host(int device, int mode, size_t S, const int64_t* row, 
     }
 }
 
-double shyft_hip_resample_last_ms(int device) { return g_rs_last_ms.load(device, 0.0); }
+double shyft_hip_resample_last_ms(int device) { return g_rs.last_ms.load(device, 0.0); }
 
-uint64_t shyft_hip_resample_calls(int device) { return g_rs_calls.load(device, 0); }
+uint64_t shyft_hip_resample_calls(int device) { return g_rs.calls.load(device, 0); }
 
-int shyft_hip_resample_last_path(int device) { return g_rs_last_path.load(device, SHYFT_HIP_RESAMPLE_PATH_AUTO); }
+int shyft_hip_resample_last_path(int device) { return g_rs.last_path.load(device, SHYFT_HIP_RESAMPLE_PATH_AUTO); }
 
 int shyft_hip_resample_set_path(int path) {
     if (path != SHYFT_HIP_RESAMPLE_PATH_AUTO && path != SHYFT_HIP_RESAMPLE_PATH_DIRECT &&

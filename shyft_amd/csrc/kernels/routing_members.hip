@@ -184,7 +184,7 @@ inline double rm_conv_at(const double* w, int L, const double* s, size_t t) {
     return v;
 }
 
-per_device<double> g_rm_ms;
+call_record g_rm;
 
 unsigned rm_grid(int64_t items) { return unsigned(std::min<int64_t>(items, RM_MAX_GRID)); }
 
@@ -296,13 +296,13 @@ int shyft_hip_route_members(int device, size_t n_members, const int64_t* group_r
             if (upstream) dc.download(upstream, a.upstream, PRT, "download upstream");
             dc.download(output, a.output, PRT, "download output");
         }
-        g_rm_ms.store(dc.dev, dc.finish("route_members sync"));
+        g_rm.record(dc.dev, dc.finish("route_members sync"));
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
     }
     return 0;
 }
 
-double shyft_hip_route_members_last_ms(int device) { return g_rm_ms.load(device, 0.0); }
+double shyft_hip_route_members_last_ms(int device) { return g_rm.last_ms.load(device, 0.0); }
 
 }  // extern "C"

@@ -5,37 +5,19 @@
 //
 // Series are [step][cell]. One workgroup reduces one step (and, for segment
 // sums, one catchment): lanes stride over the selected cells in a fixed order,
-// then a fixed-shape wavefront shuffle tree + LDS combine, so results are
-// bitwise reproducible run to run (no float atomics).
+// then a fixed-shape wavefront shuffle tree + LDS combine (block_sum of
+// device/workgroup.h), so results are bitwise reproducible run to run (no
+// float atomics).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 
+#include "../device/workgroup.h"
 #include "../include_internal/kernels.h"
 
 namespace {
 
 constexpr int RB = 256;  // 4 wavefronts
-
-__device__ inline double wave_sum(double v) {
-    // fixed butterfly over 64 lanes
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ inline double block_sum(double v) {
-    __shared__ double part[RB / 64];
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) part[wid] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-        r = part[0];
-        for (int w = 1; w < RB / 64; ++w) r += part[w];
-    }
-    return r;
-}
 
 __global__ __launch_bounds__(RB) void select_sum_kernel(const double* __restrict__ series, size_t n_cells,
                                                         const int32_t* __restrict__ cells, size_t n_sel,
@@ -48,7 +30,7 @@ __global__ __launch_bounds__(RB) void select_sum_kernel(const double* __restrict
     } else {
         for (size_t k = threadIdx.x; k < n_sel; k += RB) acc += row[cells[k]];
     }
-    const double r = block_sum(acc);
+    const double r = block_sum<RB>(acc);
     if (threadIdx.x == 0) out[t] = r;
 }
 
@@ -80,7 +62,7 @@ __global__ __launch_bounds__(RB) void segment_sum_kernel(const double* __restric
         const int32_t i = ID ? k : seg_cells[k];
         acc += W ? row[i] * w[i] : row[i];
     }
-    const double r = block_sum(acc);
+    const double r = block_sum<RB>(acc);
     if (threadIdx.x == 0) out[c * n_steps + t] = r;
 }
 

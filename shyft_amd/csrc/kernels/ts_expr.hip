@@ -28,7 +28,8 @@
 // a LOAD_RAW names a terminal with exactly as many points as the expression, so v[row[term] + i] with i below the
 // expression's point count is the terminal's own. A wavefront w < W = wrow[E] finds the e < E with wrow[e] <= w <
 // wrow[e+1], and a lane works only when its point orow[e] + i lies below orow[e+1]. te_at reads points 0 .. n - 1 of
-// its terminal only: point i + 1 after the test i + 1 < n.
+// its terminal only: point i + 1 after the test i + 1 < n; its search (first_false, device/workgroup.h) asks about
+// points below n.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -38,6 +39,7 @@
 #include <vector>
 
 #include "../../../detmath/detmath.h"
+#include "../device/csr_series.h"
 #include "../device/ts_area.h"
 #include "../host/ts_expr.hpp"
 #include "../include_internal/device_call.h"
@@ -90,13 +92,7 @@ __device__ inline double te_at(const int64_t* __restrict__ t, const double* __re
     if (n == 0 || tx < t[0] || tx >= t_end) return rs_nan();
     int64_t i = n - 1;
     if (tx < t[n - 1]) {  // upper_bound - 1; t[0] <= tx < t[n-1]
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t m = lo + ((hi - lo) >> 1);
-            if (t[m] <= tx) lo = m + 1;
-            else hi = m;
-        }
-        i = lo - 1;
+        i = first_false(int64_t(0), n, [&](int64_t m) { return t[m] <= tx; }) - 1;
     }
     const double vi = v[i];
     if (fx == int32_t(shyft_hip::host::POINT_INSTANT_VALUE) && i + 1 < n) {
@@ -115,13 +111,7 @@ __global__ __launch_bounds__(TE_BLOCK) void te_kernel(te_args a) {
     const int tid = int(threadIdx.x), lane = tid & 63;
     const int64_t stride = int64_t(gridDim.x) * TE_WAVES;
     for (int64_t w = int64_t(blockIdx.x) * TE_WAVES + (tid >> 6); w < a.W; w += stride) {
-        int32_t lo = 0, hi = a.E;  // upper_bound of w in wrow[1 .. E]
-        while (lo < hi) {
-            const int32_t m = lo + ((hi - lo) >> 1);
-            if (a.wrow[m + 1] <= w) lo = m + 1;
-            else hi = m;
-        }
-        const int32_t e = __builtin_amdgcn_readfirstlane(lo);
+        const int32_t e = __builtin_amdgcn_readfirstlane(csr_series_of(a.wrow, a.E, w));
         const int64_t o0 = a.orow[e], o1 = a.orow[e + 1];
         const int64_t i = (w - a.wrow[e]) * 64 + lane;  // the point of the expression
         if (o0 + i >= o1) continue;
@@ -203,8 +193,7 @@ te_checked te_prepare(const char* who, size_t S, const int64_t* row, const int64
     return c;
 }
 
-per_device<double> g_te_last_ms;
-per_device<uint64_t> g_te_calls;
+call_record g_te;
 constexpr const char* TE_UPLOAD = "ts_expr upload";
 
 }  // namespace
@@ -250,14 +239,10 @@ int shyft_hip_ts_expr(int device, size_t S, const int64_t* row, const int64_t* t
         d_out.alloc(no);
         te_args a{W, int32_t(E), d_row.p, d_t.p, d_v.p, d_tend.p, d_fx.p, d_prog_row.p, d_prog.p, d_consts.p,
                   d_periods.p, d_orow.p, d_ot.p, d_wrow.p, d_out.p};
-        const int64_t max_grid = int64_t(1) << 20, blocks = (W + TE_WAVES - 1) / TE_WAVES;  // the stride loop takes the rest
         c.begin();
-        hipLaunchKernelGGL(te_kernel, dim3(unsigned(blocks < max_grid ? blocks : max_grid)), dim3(TE_BLOCK), 0, c.s, a);
+        hipLaunchKernelGGL(te_kernel, dim3(launch_blocks(size_t(W + TE_WAVES - 1) / TE_WAVES)), dim3(TE_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "ts_expr");
-        c.end();
-        c.download(out, d_out.p, no, "ts_expr download");
-        g_te_last_ms.store(c.dev, c.finish("ts_expr"));
-        g_te_calls.fetch_add(c.dev, 1);
+        g_te.finish(c, "ts_expr", out, d_out.p, no);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -284,8 +269,8 @@ int shyft_hip_ts_expr_host(int device, size_t S, const int64_t* row, const int64
     }
 }
 
-double shyft_hip_ts_expr_last_ms(int device) { return g_te_last_ms.load(device, 0.0); }
+double shyft_hip_ts_expr_last_ms(int device) { return g_te.last_ms.load(device, 0.0); }
 
-uint64_t shyft_hip_ts_expr_calls(int device) { return g_te_calls.load(device, 0); }
+uint64_t shyft_hip_ts_expr_calls(int device) { return g_te.calls.load(device, 0); }
 
 }  // extern "C"

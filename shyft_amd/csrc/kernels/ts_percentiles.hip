@@ -11,7 +11,7 @@
 // host/ts_percentiles.hpp holds the same statements in plain C++ and is the definition of correct;
 // shyft_hip_ts_percentiles_host runs those, not this file's.
 //
-//  keys     every sample maps to the order-preserving 64-bit key of device/pct_plan.h, a non-finite one to the
+//  keys     every sample maps to the order-preserving 64-bit key of device/workgroup.h, a non-finite one to the
 //           all-ones sentinel (above the key of every finite value), so the order statistics are exact integer
 //           selections. +0.0 and -0.0 are different keys that compare equal as doubles: the sign of a zero result is
 //           unspecified, as for the cell percentiles.
@@ -21,7 +21,8 @@
 //  LDS      S <= SHYFT_HIP_TS_PERCENTILES_MAX_SERIES: one workgroup per interval. Lanes stride over the views, compact
 //           the finite keys into a power-of-two LDS array (at most 32 KiB; the slot comes from an integer LDS counter,
 //           and as a full sort follows the order of arrival cannot change a result), pad it with sentinels and
-//           bitonic-sort it there, as pct_lds_sort_kernel does.
+//           bitonic-sort it there (lds_sort_pad and lds_bitonic_sort of device/workgroup.h, which
+//           pct_lds_sort_kernel of kernels/percentiles.hip calls too).
 //  0..100   reads ranks min(rank, nf - 1) through pct_make_plan; lower + delta * (upper - lower) is a separately
 //           rounded multiply and add (-ffp-contract=off).
 //  -1       the sorted finite samples added in sorted order by one lane, divided by nf: the host's sum, bit for bit.
@@ -54,12 +55,12 @@
 // Index safety. The host checks before the launch that row[0] == 0 and row is non-decreasing, so stored series r has
 // the points t[row[r] .. row[r+1]) inside the uploaded row[R] points, that its times increase strictly and t_end lies
 // after the last, and that every src[s] is in [0, R). A view index is < S and an interval index < T. rs_area reads
-// point k only with k < n (device/ts_area.h); a series without points is never read. A lower-bound search reads t[m]
-// with lo <= m < hi <= n only, and the fold runs over [lo, hi) inside [0, n). ps - shift and pe - shift cannot
+// point k only with k < n (device/ts_area.h); a series without points is never read. A lower-bound search (first_false,
+// device/workgroup.h) reads t[m] with lo <= m < hi <= n only, and the fold runs over [lo, hi) inside [0, n). ps - shift and pe - shift cannot
 // overflow: the host keeps the axis, the shifts and the moved series inside a quarter of the int64 range. The WAVE
 // sort moves keys between the 64 lanes of a wavefront and reads lane min(rank, nf - 1) < 64. The LDS array has P
 // keys, P the power of two >= S sized by the launcher; at most S <= P slots are taken by the compaction, the pad and
-// the sort index below Q <= P, the power of two >= nf, and ranks are read at min(rank, nf - 1). out is written at
+// the sort index below Q <= P, the power of two >= nf (device/workgroup.h), and ranks are read at min(rank, nf - 1). out is written at
 // [e][i] with e < n_pct and i < T only. An interval without a finite sample writes NaN and reads no key.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -72,6 +73,7 @@
 
 #include "../device/pct_plan.h"
 #include "../device/ts_area.h"
+#include "../device/workgroup.h"
 #include "../host/ts_percentiles.hpp"
 #include "../include_internal/device_call.h"
 #include "../include_internal/kernels.h"
@@ -118,17 +120,6 @@ __device__ inline double tp_sample(const tp_args& a, int s, int64_t ps) {
     return tsum > 0 ? area / rs_seconds(tsum) : rs_nan();
 }
 
-// the first k in [lo, n) with t[k] >= x
-__device__ inline int64_t tp_lower_bound(const int64_t* __restrict__ t, int64_t lo, int64_t n, int64_t x) {
-    int64_t hi = n;
-    while (lo < hi) {
-        const int64_t m = lo + ((hi - lo) >> 1);
-        if (t[m] < x) lo = m + 1;
-        else hi = m;
-    }
-    return lo;
-}
-
 // the finite point values of view s inside [ps, pe) folded into kmin / kmax in key space (the closed form above)
 __device__ inline void tp_extremes(const tp_args& a, int s, int64_t ps, int64_t pe, uint64_t& kmin, uint64_t& kmax) {
     const int32_t r = a.src[s];
@@ -139,8 +130,9 @@ __device__ inline void tp_extremes(const tp_args& a, int s, int64_t ps, int64_t 
     if (a.t_end[r] + sh <= a.ta_t0) return;
     const int64_t* __restrict__ t = a.t + r0;
     const double* __restrict__ v = a.v + r0;
-    const int64_t lo = tp_lower_bound(t, 0, n, ps - sh);
-    const int64_t hi = tp_lower_bound(t, lo, n, pe - sh);
+    // the first points at or after ps and pe on the stored times
+    const int64_t lo = first_false(int64_t(0), n, [&](int64_t m) { return t[m] < ps - sh; });
+    const int64_t hi = first_false(lo, n, [&](int64_t m) { return t[m] < pe - sh; });
     for (int64_t k = lo; k < hi; ++k) {
         uint64_t key;
         if (key_of(v[k], key)) {
@@ -150,40 +142,13 @@ __device__ inline void tp_extremes(const tp_args& a, int s, int64_t ps, int64_t 
     }
 }
 
-__device__ inline uint64_t tp_wave_min(uint64_t k) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t o = __shfl_xor(k, off, 64);
-        k = o < k ? o : k;
-    }
-    return k;
-}
-__device__ inline uint64_t tp_wave_max(uint64_t k) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t o = __shfl_xor(k, off, 64);
-        k = o > k ? o : k;
-    }
-    return k;
-}
-
-// bitonic sort of one key per lane, ascending by lane
-__device__ inline uint64_t tp_wave_sort(uint64_t key, int lane) {
-    for (int k = 2; k <= 64; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const uint64_t o = __shfl_xor(key, j, 64);
-            const bool up = (lane & k) == 0, low = (lane & j) == 0;
-            const uint64_t mn = key < o ? key : o, mx = key < o ? o : key;
-            key = low == up ? mn : mx;
-        }
-    return key;
-}
-
 // entry e of one interval from the plan's two sorted samples, the sorted sum and the folded extremes
 __device__ inline double tp_entry(int64_t p, const pct_plan& q, double lower, double upper, double avg, uint64_t kmin,
                                   uint64_t kmax) {
-    if (p == -1000) return kmin == TP_NONE_MIN ? pct_nan() : value_of(kmin);
-    if (p == 1000) return kmax == TP_NONE_MAX ? pct_nan() : value_of(kmax);
+    if (p == -1000) return kmin == TP_NONE_MIN ? rs_nan() : value_of(kmin);
+    if (p == 1000) return kmax == TP_NONE_MAX ? rs_nan() : value_of(kmax);
     if (q.kind == PCT_AVG) return avg;
-    if (q.kind == PCT_NAN) return pct_nan();
+    if (q.kind == PCT_NAN) return rs_nan();
     return pct_value(q, lower, upper);
 }
 
@@ -199,9 +164,9 @@ __global__ __launch_bounds__(TP_BLOCK) void ts_percentiles_wave_kernel(tp_args a
             if (!finite) key = TP_NONE_MIN;
         }
         const int nf = __popcll(__ballot(finite));
-        double avg = pct_nan();
+        double avg = rs_nan();
         if (a.sort) {
-            key = tp_wave_sort(key, lane);
+            key = wave_bitonic_sort(key, lane);
             if (a.any_avg && nf > 0) {
                 double sum = 0.0;
                 for (int r = 0; r < nf; ++r) sum += value_of(__shfl(key, r, 64));  // in sorted order, as the host adds
@@ -211,8 +176,8 @@ __global__ __launch_bounds__(TP_BLOCK) void ts_percentiles_wave_kernel(tp_args a
         uint64_t kmin = TP_NONE_MIN, kmax = TP_NONE_MAX;
         if (a.extremes) {
             if (lane < a.S) tp_extremes(a, lane, ps, pe, kmin, kmax);
-            kmin = tp_wave_min(kmin);
-            kmax = tp_wave_max(kmax);
+            kmin = wave_reduce(kmin, op_min());
+            kmax = wave_reduce(kmax, op_max());
         }
         const int e = lane < a.pl.n ? lane : 0;
         const int64_t p = a.pl.p[e];
@@ -247,38 +212,21 @@ __global__ __launch_bounds__(TP_BLOCK) void ts_percentiles_lds_kernel(tp_args a,
             }
             __syncthreads();
             nf = int(n_fin);
-            int Q = 1;  // power of two >= nf, <= P
-            while (Q < nf) Q <<= 1;
-            for (int x = nf + int(threadIdx.x); x < Q; x += TP_BLOCK) keys[x] = TP_NONE_MIN;
+            const int Q = lds_sort_pad<false>(keys, nullptr, nf, int(threadIdx.x), TP_BLOCK);  // power of two >= nf, <= P
             __syncthreads();
-            for (int k = 2; k <= Q; k <<= 1) {
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int x = int(threadIdx.x); x < Q; x += TP_BLOCK) {
-                        const int y = x ^ j;
-                        if (y > x) {
-                            const uint64_t c = keys[x], d = keys[y];
-                            const bool up = (x & k) == 0;
-                            if ((c > d) == up) {
-                                keys[x] = d;
-                                keys[y] = c;
-                            }
-                        }
-                    }
-                    __syncthreads();
-                }
-            }
+            lds_bitonic_sort<false, false>(keys, nullptr, Q, int(threadIdx.x), TP_BLOCK);
         }
         // one lane adds the sorted samples in order, as the host does, while the other wavefronts fold the extremes
         if (threadIdx.x == 0 && a.any_avg) {
             double sum = 0.0;
             for (int r = 0; r < nf; ++r) sum += value_of(keys[r]);
-            avg_s = nf > 0 ? sum / double(nf) : pct_nan();
+            avg_s = nf > 0 ? sum / double(nf) : rs_nan();
         }
         if (a.extremes) {
             uint64_t kmin = TP_NONE_MIN, kmax = TP_NONE_MAX;
             for (int s = int(threadIdx.x); s < a.S; s += TP_BLOCK) tp_extremes(a, s, ps, pe, kmin, kmax);
-            kmin = tp_wave_min(kmin);
-            kmax = tp_wave_max(kmax);
+            kmin = wave_reduce(kmin, op_min());
+            kmax = wave_reduce(kmax, op_max());
             if (lane == 0) {
                 part_min[wave] = kmin;
                 part_max[wave] = kmax;
@@ -295,13 +243,13 @@ __global__ __launch_bounds__(TP_BLOCK) void ts_percentiles_lds_kernel(tp_args a,
                     kmin = part_min[w] < kmin ? part_min[w] : kmin;
                     kmax = part_max[w] > kmax ? part_max[w] : kmax;
                 }
-            double lower = pct_nan(), upper = pct_nan();
+            double lower = rs_nan(), upper = rs_nan();
             if (q.kind == PCT_SINGLE || q.kind == PCT_LERP) {  // nf > 0
                 const uint32_t last = uint32_t(nf - 1);
                 lower = value_of(keys[q.lo < last ? q.lo : last]);
                 upper = value_of(keys[q.hi < last ? q.hi : last]);
             }
-            a.out[int64_t(e) * a.T + i] = tp_entry(p, q, lower, upper, a.any_avg ? avg_s : pct_nan(), kmin, kmax);
+            a.out[int64_t(e) * a.T + i] = tp_entry(p, q, lower, upper, a.any_avg ? avg_s : rs_nan(), kmin, kmax);
         }
         __syncthreads();  // keys, avg_s and the parts are reused by the next round
     }
@@ -327,9 +275,7 @@ bool tp_prepare(const char* who, size_t R, const int64_t* row, const int64_t* t,
     return false;
 }
 
-per_device<double> g_tp_last_ms;
-per_device<uint64_t> g_tp_calls;
-per_device<int> g_tp_last_path;
+call_record g_tp;
 std::atomic<int> g_tp_path{SHYFT_HIP_TS_PERCENTILES_PATH_AUTO};
 constexpr const char* TP_UPLOAD = "ts_percentiles upload";
 
@@ -389,24 +335,19 @@ int shyft_hip_ts_percentiles(int device, size_t R, const int64_t* row, const int
         a.out = d_out.p;
         const bool wave = knob == SHYFT_HIP_TS_PERCENTILES_PATH_WAVE ||
                           (knob == SHYFT_HIP_TS_PERCENTILES_PATH_AUTO && S <= size_t(TP_WAVE_MAX));
-        const size_t max_grid = size_t(1) << 20;  // the grid-stride loops take the rest
         c.begin();
         if (wave) {
-            const size_t blocks = (T + TP_WAVES - 1) / TP_WAVES;
-            hipLaunchKernelGGL(ts_percentiles_wave_kernel, dim3(unsigned(blocks < max_grid ? blocks : max_grid)),
+            hipLaunchKernelGGL(ts_percentiles_wave_kernel, dim3(launch_blocks((T + TP_WAVES - 1) / TP_WAVES)),
                                dim3(TP_BLOCK), 0, c.s, a);
         } else {
             int P = 1;
             while (size_t(P) < S) P <<= 1;
-            hipLaunchKernelGGL(ts_percentiles_lds_kernel, dim3(unsigned(T < max_grid ? T : max_grid)), dim3(TP_BLOCK),
+            hipLaunchKernelGGL(ts_percentiles_lds_kernel, dim3(launch_blocks(T)), dim3(TP_BLOCK),
                                size_t(P) * sizeof(uint64_t), c.s, a, P);
         }
         hip_check(hipGetLastError(), "ts_percentiles");
-        c.end();
-        c.download(out, d_out.p, n_pct * T, "ts_percentiles download");
-        g_tp_last_ms.store(c.dev, c.finish("ts_percentiles"));
-        g_tp_last_path.store(c.dev, wave ? SHYFT_HIP_TS_PERCENTILES_PATH_WAVE : SHYFT_HIP_TS_PERCENTILES_PATH_LDS);
-        g_tp_calls.fetch_add(c.dev, 1);
+        g_tp.finish(c, "ts_percentiles", out, d_out.p, n_pct * T,
+                    wave ? SHYFT_HIP_TS_PERCENTILES_PATH_WAVE : SHYFT_HIP_TS_PERCENTILES_PATH_LDS);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -433,12 +374,12 @@ int shyft_hip_ts_percentiles_host(int device, size_t R, const int64_t* row, cons
     }
 }
 
-double shyft_hip_ts_percentiles_last_ms(int device) { return g_tp_last_ms.load(device, 0.0); }
+double shyft_hip_ts_percentiles_last_ms(int device) { return g_tp.last_ms.load(device, 0.0); }
 
-uint64_t shyft_hip_ts_percentiles_calls(int device) { return g_tp_calls.load(device, 0); }
+uint64_t shyft_hip_ts_percentiles_calls(int device) { return g_tp.calls.load(device, 0); }
 
 int shyft_hip_ts_percentiles_last_path(int device) {
-    return g_tp_last_path.load(device, SHYFT_HIP_TS_PERCENTILES_PATH_AUTO);
+    return g_tp.last_path.load(device, SHYFT_HIP_TS_PERCENTILES_PATH_AUTO);
 }
 
 int shyft_hip_ts_percentiles_set_path(int path) {

@@ -347,25 +347,12 @@ void tf_prepare_decode(const char* who, size_t S, const int32_t* start_bit, cons
     for (size_t s = 0; s < S; ++s) shyft_hip::host::check_decode_arguments(start_bit[s], n_bits[s]);
 }
 
-per_device<double> g_tf_last_ms;
-per_device<uint64_t> g_tf_calls;
-per_device<int> g_tf_last_path;
+call_record g_tf;
 std::atomic<int> g_tf_path{SHYFT_HIP_TSFILTER_PATH_AUTO};
 constexpr const char* TF_UPLOAD = "tsfilter upload";
 
-// after the last launch: the end of the timed part, the result, and the device's counters
-void tf_finish(device_call& c, double* out, const double* d_out, size_t count) {
-    c.end();
-    c.download(out, d_out, count, "tsfilter download");
-    g_tf_last_ms.store(c.dev, c.finish("tsfilter"));
-    g_tf_calls.fetch_add(c.dev, 1);
-}
-
-unsigned tf_grid(size_t jobs) {
-    const size_t max_grid = size_t(1) << 20;  // the grid-stride loops take the rest
-    const size_t blocks = (jobs + TF_BLOCK - 1) / TF_BLOCK;
-    return unsigned(blocks < max_grid ? (blocks ? blocks : 1) : max_grid);
-}
+// one lane per job; the grid-stride loops take what the grid does not
+unsigned tf_grid(size_t jobs) { return launch_blocks((jobs + TF_BLOCK - 1) / TF_BLOCK); }
 
 }  // namespace
 
@@ -415,15 +402,12 @@ int shyft_hip_ts_convolve_w(int device, size_t S, const int64_t* row, const int6
                        d_tile_s.p, d_tile_i0.p, d_out.p};
         c.begin();
         if (tiled) {
-            const size_t max_grid = size_t(1) << 20;
-            hipLaunchKernelGGL(tf_convolve_tiled_kernel, dim3(unsigned(ntiles < max_grid ? ntiles : max_grid)),
-                               dim3(TF_BLOCK), 0, c.s, a);
+            hipLaunchKernelGGL(tf_convolve_tiled_kernel, dim3(launch_blocks(ntiles)), dim3(TF_BLOCK), 0, c.s, a);
         } else {
             hipLaunchKernelGGL(tf_convolve_direct_kernel, dim3(tf_grid(np)), dim3(TF_BLOCK), 0, c.s, a);
         }
         hip_check(hipGetLastError(), "tsfilter convolve_w");
-        tf_finish(c, out, d_out.p, np);
-        g_tf_last_path.store(c.dev, tiled ? SHYFT_HIP_TSFILTER_PATH_TILED : SHYFT_HIP_TSFILTER_PATH_DIRECT);
+        g_tf.finish(c, "tsfilter", out, d_out.p, np, tiled ? SHYFT_HIP_TSFILTER_PATH_TILED : SHYFT_HIP_TSFILTER_PATH_DIRECT);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -474,7 +458,7 @@ int shyft_hip_ts_derivative(int device, size_t S, const int64_t* row, const int6
         c.begin();
         hipLaunchKernelGGL(tf_derivative_kernel, dim3(tf_grid(np)), dim3(TF_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsfilter derivative");
-        tf_finish(c, out, d_out.p, np);
+        g_tf.finish(c, "tsfilter", out, d_out.p, np);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -523,7 +507,7 @@ int shyft_hip_ts_inside(int device, size_t S, const int64_t* row, const int64_t*
         c.begin();
         hipLaunchKernelGGL(tf_inside_kernel, dim3(tf_grid(np)), dim3(TF_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsfilter inside");
-        tf_finish(c, out, d_out.p, np);
+        g_tf.finish(c, "tsfilter", out, d_out.p, np);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -574,7 +558,7 @@ int shyft_hip_ts_decode(int device, size_t S, const int64_t* row, const int64_t*
         c.begin();
         hipLaunchKernelGGL(tf_decode_kernel, dim3(tf_grid(np)), dim3(TF_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsfilter decode");
-        tf_finish(c, out, d_out.p, np);
+        g_tf.finish(c, "tsfilter", out, d_out.p, np);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -599,11 +583,11 @@ int shyft_hip_ts_decode_host(int device, size_t S, const int64_t* row, const int
     }
 }
 
-double shyft_hip_tsfilter_last_ms(int device) { return g_tf_last_ms.load(device, 0.0); }
+double shyft_hip_tsfilter_last_ms(int device) { return g_tf.last_ms.load(device, 0.0); }
 
-uint64_t shyft_hip_tsfilter_calls(int device) { return g_tf_calls.load(device, 0); }
+uint64_t shyft_hip_tsfilter_calls(int device) { return g_tf.calls.load(device, 0); }
 
-int shyft_hip_tsfilter_last_path(int device) { return g_tf_last_path.load(device, SHYFT_HIP_TSFILTER_PATH_AUTO); }
+int shyft_hip_tsfilter_last_path(int device) { return g_tf.last_path.load(device, SHYFT_HIP_TSFILTER_PATH_AUTO); }
 
 int shyft_hip_tsfilter_set_path(int path) {
     if (path != SHYFT_HIP_TSFILTER_PATH_AUTO && path != SHYFT_HIP_TSFILTER_PATH_DIRECT &&

@@ -17,8 +17,8 @@
 //           rs_area (device/ts_area.h, the device form of accumulate_value) over [t - window, t) after the policy's
 //           clip. Neighbouring lanes are neighbouring queries of one series.
 //  RECESSION and FILL are index scans over the flat point array, each in three launches: tp_scan_block_kernel (a
-//           workgroup scans TP_SPAN keys: per-lane runs, wavefront shuffles, LDS between the wavefronts, and stores the
-//           running maxima and its aggregate), tp_scan_agg_kernel (one workgroup scans the aggregates in order), and
+//           workgroup scans TP_SPAN keys: per-lane runs, then block_scan of device/workgroup.h over the lanes, and stores
+//           the running maxima and its aggregate), tp_scan_agg_kernel (one workgroup scans the aggregates in order), and
 //           the finish kernel, which combines the two and computes the value exactly as the host statement does.
 //
 // Why the scans equal the literal walks.
@@ -43,10 +43,11 @@
 // were uploaded, that times increase strictly in a series and t_end lies after the last, that pack_of[s] < P and the
 // three CSR levels of the packs are non-decreasing and end at the uploaded sizes, and that qrow is a CSR of nq
 // queries. A lane's point k (or query j) is < np (< nq) by its grid-stride test; csr_series_of (device/csr_series.h)
-// returns the s < S with row[s] <= k < row[s+1], which exists because k < row[S]. RATING reads curve it in [c0, c1) after the `c0 == c1` test
-// and segment g in [g0, g1) after `g0 == g1`. ICE passes rs_area the n > 0 points of one series (device/ts_area.h
+// returns the s < S with row[s] <= k < row[s+1], which exists because k < row[S]. RATING's two searches (first_false,
+// device/workgroup.h) ask about curves in [c0, c1) and segments in [g0, g1) only; it reads curve it in [c0, c1) after
+// the `c0 == c1` test and segment g in [g0, g1) after `g0 == g1`. ICE passes rs_area the n > 0 points of one series (device/ts_area.h
 // states its own reads). The scan kernels read key sources at positions < np only and write L at positions < np and
-// agg at block indexes < nb; LDS is indexed by the wavefront number < 4. The finish kernels read L[k - 1] only with
+// agg at block indexes < nb; LDS is indexed by the wavefront number < 4 (block_scan, device/workgroup.h). The finish kernels read L[k - 1] only with
 // k > row[s] >= 0, the mirrored L at np - 2 - k only with k + 1 < row[s+1] <= np, agg[b - 1] only with b > 0, and
 // points p, q, stop only after the tests row[s] <= p, q < row[s+1], row[s] <= stop < k. RECESSION reads point k + 1
 // only with k + 1 < row[s+1].
@@ -62,6 +63,7 @@
 #include "../../../detmath/detmath.h"
 #include "../device/csr_series.h"
 #include "../device/ts_area.h"
+#include "../device/workgroup.h"
 #include "../host/ts_prep.hpp"
 #include "../include_internal/device_call.h"
 #include "../include_internal/series_args.h"
@@ -107,25 +109,16 @@ __global__ __launch_bounds__(TP_BLOCK) void tp_rating_kernel(tp_rating_args a) {
         const double level = a.v[k];
         double r = rs_nan();
         if (c0 != c1) {
-            int64_t lo = c0, hi = c1;  // lower_bound: the first curve with start >= tk
-            while (lo < hi) {
-                const int64_t m = lo + ((hi - lo) >> 1);
-                if (a.curve_t[m] < tk) lo = m + 1;
-                else hi = m;
-            }
-            int64_t it = lo;
+            // lower_bound: the first curve with start >= tk
+            int64_t it = first_false(c0, c1, [&](int64_t m) { return a.curve_t[m] < tk; });
             bool none = false;
             if (it == c0 && a.curve_t[it] > tk) none = true;
             else if (it == c1 || a.curve_t[it] > tk) --it;
             if (!none) {
                 const int64_t g0 = a.curve_row[it], g1 = a.curve_row[it + 1];
                 if (g0 != g1) {
-                    int64_t l2 = g0, h2 = g1;  // lower_bound on `lower < level`
-                    while (l2 < h2) {
-                        const int64_t m = l2 + ((h2 - l2) >> 1);
-                        if (a.seg[4 * m] < level) l2 = m + 1;
-                        else h2 = m;
-                    }
+                    // lower_bound on `lower < level`
+                    const int64_t l2 = first_false(g0, g1, [&](int64_t m) { return a.seg[4 * m] < level; });
                     int64_t g = -1;
                     if (l2 != g1 && level == a.seg[4 * l2]) g = l2;
                     else if (l2 != g0) g = l2 - 1;
@@ -197,34 +190,9 @@ struct tp_scan_args {
 
 __device__ inline int64_t tp_max(int64_t a, int64_t b) { return a > b ? a : b; }
 
-// inclusive running maximum over the 64 lanes of a wavefront
-__device__ inline int64_t tp_wave_scan(int64_t x, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t o = __shfl_up(x, d, 64);
-        if (lane >= d) x = tp_max(x, o);
-    }
-    return x;
-}
-
-// inclusive running maximum over the workgroup's lanes in thread order; `total` is the maximum over all of them.
-// Every lane of the workgroup calls it (two barriers).
-__device__ inline int64_t tp_block_scan(int64_t x, int64_t* wsum, int64_t& total) {
-    const int lane = int(threadIdx.x & 63), wave = int(threadIdx.x >> 6);
-    x = tp_wave_scan(x, lane);
-    __syncthreads();  // wsum of the previous round has been read
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int64_t before = -1;
-    total = -1;
-#pragma unroll
-    for (int w = 0; w < TP_BLOCK / 64; ++w) {
-        const int64_t y = wsum[w];
-        if (w < wave) before = tp_max(before, y);
-        total = tp_max(total, y);
-    }
-    return tp_max(x, before);
-}
+// The scans are inclusive running maxima over the workgroup's lanes in thread order, -1 for none (block_scan,
+// device/workgroup.h; every lane of the workgroup calls it).
+static_assert(TP_BLOCK == SCAN_BLOCK, "block_scan takes a workgroup of TP_BLOCK lanes");
 
 __global__ __launch_bounds__(TP_BLOCK) void tp_scan_block_kernel(tp_scan_args a) {
     __shared__ int64_t wsum[TP_BLOCK / 64];
@@ -250,8 +218,8 @@ __global__ __launch_bounds__(TP_BLOCK) void tp_scan_block_kernel(tp_scan_args a)
             m[u] = run;
         }
         int64_t total;
-        const int64_t incl = tp_block_scan(run, wsum, total);
-        // the maximum over the lanes before this one
+        const int64_t incl = block_scan(run, op_max(), int64_t(-1), wsum, total);
+        // the maximum over the lanes before this one: block_scan leaves the wavefronts' maxima in wsum
         int64_t before = __shfl_up(incl, 1, 64);
         if ((threadIdx.x & 63) == 0) {
             before = -1;
@@ -271,7 +239,7 @@ __global__ __launch_bounds__(TP_BLOCK) void tp_scan_agg_kernel(int64_t nb, int64
     for (int64_t b0 = 0; b0 < nb; b0 += TP_BLOCK) {  // uniform over the workgroup
         const int64_t b = b0 + threadIdx.x;
         int64_t total;
-        const int64_t incl = tp_block_scan(b < nb ? agg[b] : -1, wsum, total);
+        const int64_t incl = block_scan(b < nb ? agg[b] : int64_t(-1), op_max(), int64_t(-1), wsum, total);
         if (b < nb) agg[b] = tp_max(incl, carry);
         carry = tp_max(carry, total);
     }
@@ -467,23 +435,11 @@ void tp_prepare_recession(size_t S, const int64_t* row, const int64_t* t, const 
             h::ensure_overlap(h::utcperiod(ice_start[s], ice_end[s]), h::utcperiod(t[row[s]], t_end[s]));
 }
 
-per_device<double> g_tp_last_ms;
-per_device<uint64_t> g_tp_calls;
+call_record g_tp;
 constexpr const char* TP_UPLOAD = "tsprep upload";
 
-// after the last launch: the end of the timed part, the result, and the device's counters
-void tp_finish(device_call& c, double* out, const double* d_out, size_t count) {
-    c.end();
-    c.download(out, d_out, count, "tsprep download");
-    g_tp_last_ms.store(c.dev, c.finish("tsprep"));
-    g_tp_calls.fetch_add(c.dev, 1);
-}
-
-unsigned tp_grid(size_t jobs) {
-    const size_t max_grid = size_t(1) << 20;  // the grid-stride loops take the rest
-    const size_t blocks = (jobs + TP_BLOCK - 1) / TP_BLOCK;
-    return unsigned(blocks < max_grid ? (blocks ? blocks : 1) : max_grid);
-}
+// one lane per job; the grid-stride loops take what the grid does not
+unsigned tp_grid(size_t jobs) { return launch_blocks((jobs + TP_BLOCK - 1) / TP_BLOCK); }
 
 // the two scan launches of one key kind; L [np] and agg [nb] are allocated here
 void tp_scan(device_call& c, int kind, int64_t np, int64_t S, const int64_t* d_row, const double* d_src,
@@ -502,8 +458,7 @@ void tp_scan(device_call& c, int kind, int64_t np, int64_t S, const int64_t* d_r
     a.max_x = d_max;
     a.L = L.p;
     a.agg = agg.p;
-    const int64_t max_grid = int64_t(1) << 20;
-    hipLaunchKernelGGL(tp_scan_block_kernel, dim3(unsigned(nb < max_grid ? nb : max_grid)), dim3(TP_BLOCK), 0, c.s, a);
+    hipLaunchKernelGGL(tp_scan_block_kernel, dim3(launch_blocks(size_t(nb))), dim3(TP_BLOCK), 0, c.s, a);
     hip_check(hipGetLastError(), "tsprep scan");
     hipLaunchKernelGGL(tp_scan_agg_kernel, dim3(1), dim3(TP_BLOCK), 0, c.s, nb, agg.p);
     hip_check(hipGetLastError(), "tsprep scan of the aggregates");
@@ -539,7 +494,7 @@ int shyft_hip_ts_rating_curve(int device, size_t S, const int64_t* row, const in
         c.begin();
         hipLaunchKernelGGL(tp_rating_kernel, dim3(tp_grid(np)), dim3(TP_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsprep rating");
-        tp_finish(c, out, d_out.p, np);
+        g_tp.finish(c, "tsprep", out, d_out.p, np);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -606,7 +561,7 @@ int shyft_hip_ts_ice_packing(int device, size_t S, const int64_t* row, const int
         c.begin();
         hipLaunchKernelGGL(tp_ice_kernel, dim3(tp_grid(nq)), dim3(TP_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsprep ice packing");
-        tp_finish(c, out, d_out.p, nq);
+        g_tp.finish(c, "tsprep", out, d_out.p, nq);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -662,7 +617,7 @@ int shyft_hip_ts_ice_packing_recession(int device, size_t S, const int64_t* row,
                       d_out.p};
         hipLaunchKernelGGL(tp_rec_finish_kernel, dim3(tp_grid(np)), dim3(TP_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsprep recession");
-        tp_finish(c, out, d_out.p, np);
+        g_tp.finish(c, "tsprep", out, d_out.p, np);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -715,7 +670,7 @@ int shyft_hip_ts_min_max_fill(int device, size_t S, const int64_t* row, const in
                        aggq.p, d_out.p};
         hipLaunchKernelGGL(tp_fill_finish_kernel, dim3(tp_grid(np)), dim3(TP_BLOCK), 0, c.s, a);
         hip_check(hipGetLastError(), "tsprep fill");
-        tp_finish(c, out, d_out.p, np);
+        g_tp.finish(c, "tsprep", out, d_out.p, np);
         return 0;
     } catch (const std::exception& e) {
         return fail(nullptr, e.what());
@@ -745,8 +700,8 @@ int shyft_hip_ts_min_max_fill_host(int device, size_t S, const int64_t* row, con
     }
 }
 
-double shyft_hip_tsprep_last_ms(int device) { return g_tp_last_ms.load(device, 0.0); }
+double shyft_hip_tsprep_last_ms(int device) { return g_tp.last_ms.load(device, 0.0); }
 
-uint64_t shyft_hip_tsprep_calls(int device) { return g_tp_calls.load(device, 0); }
+uint64_t shyft_hip_tsprep_calls(int device) { return g_tp.calls.load(device, 0); }
 
 }  // extern "C"

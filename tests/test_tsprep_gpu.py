@@ -86,6 +86,41 @@ def test_recession_falls_back_to_the_series_own_first_point(region):
     assert dev.tolist() == [100.0, 200.0, 300.0, 8.0, 8.0, 8.0, 11.0]  # alpha 0: the flow where the ice began
 
 
+# One series longer than 256 scan spans: tp_scan_agg_kernel scans the span aggregates 256 at a time and carries the
+# running maximum into its second round, which starts at flat position ROUND.
+ROUND = 256 * tc.SCAN_SPAN
+NP_ROUNDS = ROUND + 1500
+
+
+def _two_round_series(seed):
+    rng = np.random.default_rng(seed)
+    t = rc.HOUR * np.arange(NP_ROUNDS, dtype=np.int64)
+    return [0, NP_ROUNDS], t, rng.uniform(0.5, 10.0, NP_ROUNDS), [rc.HOUR * NP_ROUNDS], [1]
+
+
+def test_recession_carries_the_stop_index_into_the_second_round_of_the_aggregate_scan(region):
+    """ice runs whose stop index lies in the first 256 spans and whose points lie behind them. One indicator cannot
+    hold a run across ROUND and another that starts at ROUND, so there are two; every other run is short, the host walks
+    a run of n points in about n^2 / 2 steps."""
+    assert tc.SCAN_SPAN == 1024 and ROUND == 262144
+    series = _two_round_series(77)
+    a = np.zeros(NP_ROUNDS)
+    a[261000:263500] = 1.0  # over the span boundaries 255 and 257 and over ROUND; stops at 260999
+    a[99] = NAN             # just before a short run: every point of it is lost
+    a[100:140] = 1.0
+    a[263600:] = 1.0        # to the last point
+    b = np.zeros(NP_ROUNDS)
+    b[ROUND:ROUND + 60] = 1.0   # starts exactly at ROUND: stops at the last key of the first round
+    b[261000:ROUND - 1] = 1.0   # ends one short of it
+    b[262999] = NAN
+    b[263000:263300] = 1.0      # lost, behind ROUND
+    for ice in (a, b):
+        args = (*series, ice, 0, rc.HOUR * NP_ROUNDS, 1 / (7 * 86400.0), 0.75)
+        dev = region.ts_ice_packing_recession_csr(*args)
+        _same(dev, region.ts_ice_packing_recession_csr(*args, host=True), int(ice[ROUND]))
+    assert np.isfinite(dev[ROUND:ROUND + 60]).all() and np.isnan(dev[263000:263300]).all()
+
+
 @pytest.mark.parametrize("k,S", list(enumerate(SS)))
 def test_min_max_fill_is_bit_identical_to_host(region, k, S):
     t0, dt, batch = _batch(S, k)
@@ -120,6 +155,37 @@ def test_min_max_fill_edges(region):
         assert np.allclose(dev[10:], filled, rtol=1e-12, atol=0.0, equal_nan=True), span
     edge = region.ts_min_max_fill_csr([0, 4], [0, 10, 20, 30], [50.0, 1.0, 2.0, -50.0], [40], [0], 0.0, 10.0, 1000)
     assert np.array_equal(edge, [NAN, 1.0, 2.0, NAN], equal_nan=True)  # invalid at index 0 and n - 1
+
+
+def test_min_max_fill_over_the_second_round_of_the_aggregate_scan(region):
+    """Invalid runs over flat position ROUND and over NP_ROUNDS - 1 - ROUND, where the mirrored scan meets the same
+    boundary; max_timespan fills the shorter of a pair and refuses the longer. The runs of a few hundred points find
+    their neighbours through the last aggregate of the first round or inside their own span. The two runs longer than
+    a span are the ones that need the carry: each covers the whole first span of the second round of its scan and
+    reaches into the next one, so the points there have no key in their own span nor in the aggregate before it and
+    get their neighbour from the first round through the carried maximum alone."""
+    row, t, v, t_end, fx = _two_round_series(78)
+    mirror = NP_ROUNDS - 1 - ROUND
+    short = v.copy()
+    short[ROUND - 144:ROUND + 156] = 50.0   # 300 points above max_x: neighbours 301 steps apart
+    short[mirror - 99:mirror + 101] = NAN   # 200 points: neighbours 201 steps apart
+    short[ROUND - 1000:ROUND - 990] = NAN   # short runs on either side, and at both ends of the series
+    short[ROUND + 1000:ROUND + 1003] = -50.0
+    short[:2] = NAN
+    short[-3:] = NAN
+    for span in (250 * rc.HOUR, 301 * rc.HOUR, 10 * rc.HOUR):
+        host = region.ts_min_max_fill_csr(row, t, short, t_end, fx, -1.0, 11.0, span, host=True)
+        _same(region.ts_min_max_fill_csr(row, t, short, t_end, fx, -1.0, 11.0, span), host, span)
+        assert np.isnan(host[ROUND]) == (span < 301 * rc.HOUR) and np.isnan(host[mirror]) == (span < 201 * rc.HOUR)
+    long = v.copy()
+    assert ROUND + tc.SCAN_SPAN + 132 < NP_ROUNDS and mirror - tc.SCAN_SPAN - 95 > 0
+    long[ROUND - 44:ROUND + tc.SCAN_SPAN + 132] = NAN        # 1200 points, over spans 256 and 257 of the scan
+    long[mirror - tc.SCAN_SPAN - 95:mirror + 101] = 50.0     # 1220 points, over spans 256 and 257 of the mirrored scan
+    for span in (1210 * rc.HOUR, 1221 * rc.HOUR):
+        host = region.ts_min_max_fill_csr(row, t, long, t_end, fx, -1.0, 11.0, span, host=True)
+        _same(region.ts_min_max_fill_csr(row, t, long, t_end, fx, -1.0, 11.0, span), host, span)
+        assert not np.isnan(host[ROUND + tc.SCAN_SPAN + 100])
+        assert np.isnan(host[mirror - tc.SCAN_SPAN - 50]) == (span < 1221 * rc.HOUR)
 
 
 @pytest.mark.parametrize("k,S", list(enumerate(SS)))
