@@ -199,10 +199,9 @@ __device__ __noinline__ double gs_corr_lwc(double z1, double a1, double b1, doub
     return x;
 }
 
-// per-cell constants of the snow routine
+// per-cell constants of the snow routine (the step reads the forest fraction and the altitude only through cv2)
 struct gs_cell {
-    double forest_fraction, altitude;
-    double cv2;       // effective_snow_cv(forest, altitude)^2 (gamma_snow.h:85-87)
+    double cv2;      // effective_snow_cv(forest, altitude)^2 (gamma_snow.h:85-87)
     double inv_cv2;   // 1.0/cv2
 };
 

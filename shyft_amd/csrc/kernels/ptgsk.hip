@@ -105,9 +105,9 @@ constexpr int BRENT_PRIO = 3;
 // the parameter row is then wave-uniform and lives in SGPRs (scalar loads), which frees the VGPRs the
 // per-lane copies would take in the register-bound time loop.
 // ENS: a parameter-ensemble launch (lanes = cells x members): forcing is read from the shared column fcol[lane].
-// The 11 per-cell constants live in LDS (22 KB per workgroup, 38.9 KB with the job queue: 4 workgroups = 16
-// waves per CU still fit the 160 KB) instead of VGPRs live across the Brent phase. Scratch 400 -> 320 B/lane;
-// 124.8 -> 119.1 ms per 1M-cell chunk over the bench year, bit-exact.
+// The per-cell constants and the lane's lgamma cache live in LDS (9 rows, 18 KB per workgroup, 35.3 KB with the job
+// queue: 4 workgroups = 16 waves per CU still fit the 160 KB) instead of VGPRs live across the Brent phase. Scratch
+// 400 -> 320 B/lane; 124.8 -> 119.1 ms per 1M-cell chunk over the bench year, bit-exact.
 // WAVES: the occupancy target. 4 waves per SIMD (128 VGPRs, spilling) is the measured best when the launch fills
 // the GPU; a region too small to give every SIMD 4 waves (<= 2 workgroups per CU, e.g. a strong-scaled shard of
 // 131K cells) gets the 2-wave instance instead (256 VGPRs, no spills): it cannot be 4-deep anyway.
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
     const size_t NF = ENS ? (size_t)a.f_cols : N;
     const size_t fcl = ENS ? (size_t)a.fcol[lc] : (size_t)lc;
     const double* __restrict__ Pg = UNIFORM ? a.params : a.params + (size_t)a.set_ix[lc] * PTGSK_NP;
-    // the uniform parameter row in LDS (288 B next to the 38.9 KB of job queue and cell constants): the step loop
+    // the uniform parameter row in LDS (288 B next to the 35 KB of job queue and cell constants): the step loop
     // reads it with ds_read_b64 where it is used instead of holding 36 doubles in SGPRs, which spilled to VGPR lanes
     // (a v_readlane per use) beside the inline exp / log constant table. r05: 80.8 -> 79.0 ms per 730-step chunk,
     // v_readlane_b32 326 -> 270 in the kernel's code. (Read after the first barrier below.)
@@ -138,42 +138,36 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
     // per-cell constants (pt_gs_k.h:347-357)
     const double* __restrict__ cc = a.cellc;
     gs_cell gcell;
-    gcell.forest_fraction = cc[PC_FOREST * N + lc];
-    gcell.altitude = cc[PC_ALTITUDE * N + lc];
     gcell.cv2 = cc[PC_CV2 * N + lc];
     gcell.inv_cv2 = cc[PC_INV_CV2 * N + lc];
     // the cell constants live in LDS, not in VGPRs: each use reloads its lane's slot (the barriers of the
     // step keep the compiler from hoisting the loads), so none of them is live across the Brent phase
-    // rows 0-8: the cell constants; rows 9-10: the lane's lgamma cache (shape, value), so that every per-lane LDS
+    // rows 0-6: the cell constants; rows 7-8: the lane's lgamma cache (shape, value), so that every per-lane LDS
     // slot is one address register plus an immediate offset. Two constants are formed from the others with the
     // host's own expressions (region.hip update_derived): kirchner_fraction = 1 - direct_response_fraction and
     // glacier_area_m2 = area * glacier, the same operations on the same doubles
-    __shared__ double lcc[11][B];
+    __shared__ double lcc[9][B];
     {
         const int t = threadIdx.x;
-        lcc[0][t] = gcell.forest_fraction;
-        lcc[1][t] = gcell.altitude;
-        lcc[2][t] = gcell.cv2;
-        lcc[3][t] = gcell.inv_cv2;
-        lcc[4][t] = cc[PC_GLACIER * N + lc];
-        lcc[5][t] = cc[PC_SNOW_STORAGE * N + lc];
-        lcc[6][t] = cc[PC_KIRCHNER_ROUTED_PREC * N + lc];
-        lcc[7][t] = cc[PC_DIRECT_RESPONSE * N + lc];
-        lcc[8][t] = cc[PC_AREA * N + lc];
+        lcc[0][t] = gcell.cv2;
+        lcc[1][t] = gcell.inv_cv2;
+        lcc[2][t] = cc[PC_GLACIER * N + lc];
+        lcc[3][t] = cc[PC_SNOW_STORAGE * N + lc];
+        lcc[4][t] = cc[PC_KIRCHNER_ROUTED_PREC * N + lc];
+        lcc[5][t] = cc[PC_DIRECT_RESPONSE * N + lc];
+        lcc[6][t] = cc[PC_AREA * N + lc];
     }
-#define glacier_fraction (lcc[4][threadIdx.x])
-#define snow_storage_fraction (lcc[5][threadIdx.x])
-#define kirchner_routed_prec (lcc[6][threadIdx.x])
-#define direct_response_fraction (lcc[7][threadIdx.x])
-#define kirchner_fraction (1 - lcc[7][threadIdx.x])                   // PC_KIRCHNER_FRACTION = 1 - direct
-#define cell_area_m2 (lcc[8][threadIdx.x])
-#define glacier_area_m2 (lcc[8][threadIdx.x] * lcc[4][threadIdx.x])  // PC_GLACIER_AREA = area * glacier
+#define glacier_fraction (lcc[2][threadIdx.x])
+#define snow_storage_fraction (lcc[3][threadIdx.x])
+#define kirchner_routed_prec (lcc[4][threadIdx.x])
+#define direct_response_fraction (lcc[5][threadIdx.x])
+#define kirchner_fraction (1 - lcc[5][threadIdx.x])                   // PC_KIRCHNER_FRACTION = 1 - direct
+#define cell_area_m2 (lcc[6][threadIdx.x])
+#define glacier_area_m2 (lcc[6][threadIdx.x] * lcc[2][threadIdx.x])  // PC_GLACIER_AREA = area * glacier
 #define LOAD_GCELL()                                   \
     do {                                               \
-        gcell.forest_fraction = lcc[0][threadIdx.x];   \
-        gcell.altitude = lcc[1][threadIdx.x];          \
-        gcell.cv2 = lcc[2][threadIdx.x];               \
-        gcell.inv_cv2 = lcc[3][threadIdx.x];           \
+        gcell.cv2 = lcc[0][threadIdx.x];               \
+        gcell.inv_cv2 = lcc[1][threadIdx.x];           \
     } while (0)
 
     const double mmh_to_m3s_scale_factor = 1 / (3600.0 * 1000.0);
@@ -190,12 +184,12 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
     s.iso_pot_energy = st[PS_ISO_POT_ENERGY * N + lc];
     s.temp_swe = st[PS_TEMP_SWE * N + lc];
     double q = st[PS_KIRCHNER_Q * N + lc];
-    lcc[9][threadIdx.x] = -1.0;  // the lgamma cache (device/ptgsk_dev.h)
-    lcc[10][threadIdx.x] = 0.0;
+    lcc[7][threadIdx.x] = -1.0;  // the lgamma cache (device/ptgsk_dev.h)
+    lcc[8][threadIdx.x] = 0.0;
     constexpr bool LGQ = SHYFT_PTGSK_LGQ != 0 && B == 256 && !SPEC;
     constexpr bool JOBLG = LGQ && SHYFT_PTGSK_LGQ_JOBLG != 0;
     constexpr int BOPEN = (B == 256 && !SPEC) ? SHYFT_PTGSK_BOPEN : 0;
-    lgamma_cache_lds<JOBLG> lgc{lcc[9], lcc[10]};
+    lgamma_cache_lds<JOBLG> lgc{lcc[7], lcc[8]};
     gs_carry carry;
     int32_t err = 0;
 
@@ -235,9 +229,9 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
     __shared__ int jcount[2];
     // lgamma queue of the workgroup (LGQ): the lanes whose final calc_snow_state of the step will want lgamma of a
     // shape their cache slot does not hold (gs_front's new_shape, device/ptgsk_dev.h). The owner writes the shape
-    // into its key slot lcc[9][t] and its lane id into lq; between the step's two barriers the wavefronts that are
+    // into its key slot lcc[7][t] and its lane id into lq; between the step's two barriers the wavefronts that are
     // not solving Brent jobs evaluate dlgamma of the queued shapes, one per lane, into the owners' value slots
-    // lcc[10][owner], so the owners' gs_back hits the cache instead of every wavefront running dlgamma for a few
+    // lcc[8][owner], so the owners' gs_back hits the cache instead of every wavefront running dlgamma for a few
     // of its lanes. Invariant: a slot whose key has been set holds dlgamma(key) by the time its owner next reads it
     // (DESIGN.md 3.1). The same function of the same argument: the same bits as the owner's own evaluation.
     __shared__ unsigned short lq[LGQ ? B : 1];
@@ -303,9 +297,9 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
         int slot = -1;
         bool queued = false;  // this lane has a shape in the step's lgamma queue
         auto new_shape = [&](double shape) {
-            if (LGQ && shape != lcc[9][threadIdx.x]) {
+            if (LGQ && shape != lcc[7][threadIdx.x]) {
                 lq[atomicAdd(&lcount[i & 1], 1)] = (unsigned short)threadIdx.x;
-                lcc[9][threadIdx.x] = shape;
+                lcc[7][threadIdx.x] = shape;
                 queued = true;
             }
         };
@@ -322,7 +316,7 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
                     const double lga2 = dlgamma(ja2[j]);
                     jlg2[j] = lga2;
                     const int o = jown[j];
-                    if (lcc[9][o] == ja2[j]) lcc[10][o] = lga2;
+                    if (lcc[7][o] == ja2[j]) lcc[8][o] = lga2;
                 }
             if (BOPEN) {
                 // (a group's lanes are all below 64: L nj <= 64)
@@ -338,7 +332,7 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
         auto lgamma_jobs = [&](int first, int stride, int nl) {
             for (int j = first; j < nl; j += stride) {
                 const int o = lq[j];
-                lcc[10][o] = dlgamma(lcc[9][o]);
+                lcc[8][o] = dlgamma(lcc[7][o]);
             }
         };
         // the step's Brent job goes into the queue where gs_front forms it
@@ -429,7 +423,7 @@ __global__ __launch_bounds__(B, WAVES) void ptgsk_run_kernel(const ptgsk_kargs a
                 __syncthreads();
             } else if (LGQ && queued) {
                 // no Brent job: nobody waits, so the owner evaluates its own shape (no second barrier, as before)
-                lcc[10][threadIdx.x] = dlgamma(lcc[9][threadIdx.x]);
+                lcc[8][threadIdx.x] = dlgamma(lcc[7][threadIdx.x]);
             }
         }
         PROF_MARK(2);  // Brent phase

@@ -4,6 +4,7 @@
 # usage: build_variants_ptgsk.sh name1 "flags1" name2 "flags2" ...
 # e.g. the Brent opening A/B:
 #   build_variants_ptgsk.sh bopen0 "-DSHYFT_PTGSK_BOPEN=0" bopen1 "-DSHYFT_PTGSK_BOPEN=1" bopen2 "-DSHYFT_PTGSK_BOPEN=2"
+# or the incomplete gamma's term loops (device/gamma_lean.h): gl0 "-DSHYFT_GAMMA_LOOPS=0" gl3 "-DSHYFT_GAMMA_LOOPS=3"
 # PTGSK_FLAGS: the Makefile's per-object flags of this file (set it empty to build a variant without them)
 set -e
 cd "$(dirname "$0")/../shyft_amd/csrc"

@@ -143,7 +143,7 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(&hb, bad, 4, hipMemcpyDeviceToHost));
         printf("lean vs gs_corr_lwc: %d of %d results differ\n", hb, 2 * n);
     }
-    for (int lean = 0; lean < 2; ++lean) for (int active : {64, 22}) for (int waves : {1, 1024, 4096}) {
+    for (int lean = 0; lean < 2; ++lean) for (int active : {64, 22, 16}) for (int waves : {1, 1024, 4096}) {
         const int reps = 4;
         auto go = [&]() {
             if (lean) solve2<1><<<waves, 64>>>(J, q1, lg, n, reps, active, out, cyc);
