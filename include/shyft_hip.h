@@ -129,7 +129,13 @@ int shyft_hip_set_parameters(shyft_hip_region* h, const double* params, size_t n
 
 /* Time axis (fixed_dt). Allocates forcing/response storage for a resident
  * window of window_steps steps starting at step 0 (window_steps == 0: whole axis).
- * Replaces initialize_cell_environment (region_model.h:359-364): forcing is NaN-filled. */
+ * Replaces initialize_cell_environment (region_model.h:359-364): forcing is NaN-filled.
+ * Any dt_us > 0 is taken (sub-hourly, hours, days, not a whole number of seconds), with 1 <= n_steps <= INT32_MAX,
+ * else "region_model::run with invalid time_axis invoked". Every step time t0_us + i * dt_us, i <= n_steps, must lie
+ * within +-2^62 us of 1970-01-01 (about +-146 000 years), negative times included: there the day-of-year and
+ * time-in-year tables of pt_gs_k are exact (proleptic Gregorian, UTC); an axis that leaves that range is refused
+ * ("set_time_axis: step times beyond ..."). On a region that has already run, the call also has the dt-derived
+ * pt_gs_k parameter columns rebuilt before the next run. */
 int shyft_hip_set_time_axis(shyft_hip_region* h, int64_t t0_us, int64_t dt_us, size_t n_steps, size_t window_steps);
 /* Move the resident window to start at step w0 (window length unchanged). Forcing
  * in the window becomes NaN, responses NaN. Used to stream long horizons in chunks. */

@@ -1,6 +1,7 @@
 // Internal, host only (no HIP): the index tables the region layer builds before a launch. A CSR segment table by
 // counting sort (catchment, routing-group and ensemble segments), and the tables of a river network (routing.hip,
-// routing_members.hip). tools/host_tables_check.cpp runs both under the address and undefined-behaviour sanitizers.
+// routing_members.hip), and the UTC calendar with the per-step day-of-year / time-in-year tables of pt_gs_k.
+// tools/host_tables_check.cpp runs all three under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -76,6 +77,69 @@ bool build_river_tables(size_t P, const int64_t* group_row, const int32_t* group
         for (size_t r = 0; r < R; ++r) emit(size_t(level[r]), int32_t(r));
     });
     return true;
+}
+
+// UTC civil calendar (core/utctime_utilities.cpp:230-253): the proleptic Gregorian days <-> (year, month, day) maps
+// in closed form, on days since 1970-01-01. Exact for every instant an int64 microsecond count can hold.
+inline int64_t floor_div(int64_t a, int64_t b) {
+    int64_t q = a / b;
+    if ((a % b != 0) && ((a < 0) != (b < 0))) --q;
+    return q;
+}
+inline void civil_from_days(int64_t z, int64_t& y, int& m, int& d) {
+    z += 719468;
+    const int64_t era = (z >= 0 ? z : z - 146096) / 146097;
+    const int64_t doe = z - era * 146097;
+    const int64_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
+    y = yoe + era * 400;
+    const int64_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
+    const int64_t mp = (5 * doy + 2) / 153;
+    d = int(doy - (153 * mp + 2) / 5 + 1);
+    m = int(mp < 10 ? mp + 3 : mp - 9);
+    y += (m <= 2);
+}
+inline int64_t days_from_civil(int64_t y, int m, int d) {
+    y -= m <= 2;
+    const int64_t era = (y >= 0 ? y : y - 399) / 400;
+    const int64_t yoe = y - era * 400;
+    const int64_t doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
+    const int64_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+    return era * 146097 + doe - 719468;
+}
+constexpr int64_t DAY_US = 86400LL * 1000000LL;
+
+// calendar::day_of_year (UTC, core/utctime_utilities.cpp:230-235)
+inline int day_of_year(int64_t t_us) {
+    const int64_t days = floor_div(t_us, DAY_US);
+    int64_t y;
+    int m, d;
+    civil_from_days(days, y, m, d);
+    return int(1 + days - days_from_civil(y, 1, 1));
+}
+
+// Whether every step time t0_us + i * dt_us, i <= n, lies within +-2^62 us of 1970-01-01 (about +-146 000 years):
+// there neither the step times nor the products of the calendar arithmetic leave int64. dt_us > 0, n >= 1.
+inline bool year_tables_cover(int64_t t0_us, int64_t dt_us, size_t n) {
+    constexpr int64_t LIM = int64_t(1) << 62;
+    int64_t span, end;
+    if (t0_us < -LIM || t0_us > LIM) return false;
+    if (__builtin_mul_overflow(int64_t(n), dt_us, &span) || __builtin_add_overflow(t0_us, span, &end)) return false;
+    return end <= LIM;
+}
+
+// The per-step calendar tables of pt_gs_k (gamma_snow.h:89-96) for the steps t0_us + i * dt_us, i < n:
+// doy[i] = calendar::day_of_year(t), trel[i] = t - calendar::trim(t, YEAR). The axis passes year_tables_cover.
+inline void build_year_tables(int64_t t0_us, int64_t dt_us, size_t n, int32_t* doy, int64_t* trel) {
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t t = t0_us + int64_t(i) * dt_us;
+        const int64_t days = floor_div(t, DAY_US);
+        int64_t y;
+        int m, d;
+        civil_from_days(days, y, m, d);
+        const int64_t jan1 = days_from_civil(y, 1, 1);
+        doy[i] = int32_t(1 + days - jan1);  // calendar::day_of_year
+        trel[i] = t - jan1 * DAY_US;        // t - calendar::trim(t, YEAR)
+    }
 }
 
 }  // namespace shyft_hip_impl

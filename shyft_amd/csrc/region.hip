@@ -27,43 +27,6 @@ using namespace shyft_hip_impl;
 
 namespace {
 
-// UTC civil calendar (core/utctime_utilities.cpp:230-253)
-int64_t floor_div(int64_t a, int64_t b) {
-    int64_t q = a / b;
-    if ((a % b != 0) && ((a < 0) != (b < 0))) --q;
-    return q;
-}
-void civil_from_days(int64_t z, int64_t& y, int& m, int& d) {
-    z += 719468;
-    const int64_t era = (z >= 0 ? z : z - 146096) / 146097;
-    const int64_t doe = z - era * 146097;
-    const int64_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
-    y = yoe + era * 400;
-    const int64_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
-    const int64_t mp = (5 * doy + 2) / 153;
-    d = int(doy - (153 * mp + 2) / 5 + 1);
-    m = int(mp < 10 ? mp + 3 : mp - 9);
-    y += (m <= 2);
-}
-int64_t days_from_civil(int64_t y, int m, int d) {
-    y -= m <= 2;
-    const int64_t era = (y >= 0 ? y : y - 399) / 400;
-    const int64_t yoe = y - era * 400;
-    const int64_t doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1;
-    const int64_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
-    return era * 146097 + doe - 719468;
-}
-constexpr int64_t DAY_US = 86400LL * 1000000LL;
-
-// calendar::day_of_year (UTC, core/utctime_utilities.cpp:230-235)
-int day_of_year(int64_t t_us) {
-    const int64_t days = floor_div(t_us, DAY_US);
-    int64_t y;
-    int m, d;
-    civil_from_days(days, y, m, d);
-    return int(1 + days - days_from_civil(y, 1, 1));
-}
-
 // region_model::update_ix_to_id_mapping (region_model.h:236-252)
 void update_ix_to_id_mapping(shyft_hip_region* h) {
     h->cid_to_cix.clear();
@@ -611,6 +574,8 @@ int shyft_hip_set_time_axis(shyft_hip_region* h, int64_t t0_us, int64_t dt_us, s
     return guarded(h, [&] {
         if (dt_us <= 0 || n_steps == 0) throw std::runtime_error("region_model::run with invalid time_axis invoked");
         if (n_steps > (size_t)INT32_MAX) throw std::runtime_error("time axis too long");
+        if (!year_tables_cover(t0_us, dt_us, n_steps))
+            throw std::runtime_error("set_time_axis: step times beyond +-2^62 microseconds from 1970-01-01");
         h->t0 = t0_us;
         h->dt = dt_us;
         h->T = n_steps;
@@ -618,15 +583,7 @@ int shyft_hip_set_time_axis(shyft_hip_region* h, int64_t t0_us, int64_t dt_us, s
         h->TW = (window_steps == 0 || window_steps > n_steps) ? n_steps : window_steps;
         std::vector<int32_t> doy(n_steps);
         std::vector<int64_t> trel(n_steps);
-        for (size_t i = 0; i < n_steps; ++i) {
-            const int64_t t = t0_us + int64_t(i) * dt_us;
-            const int64_t days = floor_div(t, DAY_US);
-            int64_t y; int m, d;
-            civil_from_days(days, y, m, d);
-            const int64_t jan1 = days_from_civil(y, 1, 1);
-            doy[i] = int32_t(1 + days - jan1);  // calendar::day_of_year
-            trel[i] = t - jan1 * DAY_US;        // t - calendar::trim(t, YEAR)
-        }
+        build_year_tables(t0_us, dt_us, n_steps, doy.data(), trel.data());
         h->d_doy.alloc(n_steps);
         h->d_trel.alloc(n_steps);
         hip_check(region_copy(h, h->d_doy.p, doy.data(), n_steps * sizeof(int32_t), hipMemcpyHostToDevice), "upload doy");

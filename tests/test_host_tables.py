@@ -1,5 +1,7 @@
 """The host-only index tables of the region layer (csrc/include_internal/host_tables.h): the CSR builder and the river
-network tables, checked by tools/host_tables_check.cpp under the address and undefined-behaviour sanitizers. The
+network tables, and the calendar tables of pt_gs_k (build_year_tables: day of year and time since New Year of every
+step, against a day-by-day walk over the axes of tests/time_axis_cases.py and whole years around 1900, 1970, 2000, 2016,
+2100 and 2400), checked by tools/host_tables_check.cpp under the address and undefined-behaviour sanitizers. The
 program is built and run as a child process on the CPU; nothing of it is loaded into this interpreter."""
 import pathlib
 import subprocess

@@ -15,7 +15,8 @@ tolerances, is within its own tolerance of the exact value too, so the two are w
    q in [1e-5, 40], P - E in [-0.5, 30] (default c1, c2, c3). odeint at the same tolerances is within the same
    order of the exact solution, so a controller that took different steps would differ by <= ~5e-7 relative per
    step; the restatement follows odeint's error checker and step adjuster, so the step sequence itself is the
-   same up to libm ulps (parity unpinned beyond that: no odeint here)."""
+   same up to libm ulps (parity unpinned beyond that: no odeint here). The same bound is asserted for steps of
+   15 min, 3 h and 24 h (measured worst cases in the test's docstring)."""
 import ctypes as C
 
 import numpy as np
@@ -48,22 +49,35 @@ def test_gamma_p_full_precision_matches_scipy():
 
 
 def test_kirchner_step_within_bound_of_exact():
+    for dt_s in (900, 3600, 3 * 3600, 24 * 3600):
+        _kirchner_step_within_bound_of_exact(dt_s)
+
+
+def _kirchner_step_within_bound_of_exact(dt_s):
+    """The end-of-step q of one step of 15 min, 1 h, 3 h and 24 h against DOP853 integrated to dt / 1 h, on the same
+    (q0, P - E) grid; over a longer step the controller takes more steps, with other rejections. The bound is the
+    5e-7 derived in the module docstring (two controllers, each within about 2.6e-7 of the exact solution), at every
+    step length. Worst cases measured on this grid: 1.96e-7 at 15 min, 2.53e-7 at 1 h, 1.51e-7 at 3 h, 2.32e-7 at
+    24 h. q_avg is not compared with the exact time mean: the routine averages by trapezoid over its own steps, as
+    the reference does (trapezoidal_average, kirchner.h:24-52, :213-234), which sits 1.6-5.7 % from the true mean at every dt, hourly included."""
     L = oracle_lib.load()
     c1, c2, c3 = -2.439, 0.966, -0.1
     HOUR = 3600 * 10**6
+    dt_us = dt_s * 10**6
     worst = 0.0
     for q0 in (1e-5, 1e-3, 0.05, 0.5, 1.0, 3.0, 10.0, 40.0):
         for pe in (-0.5, -0.1, 0.0, 0.2, 1.0, 3.0, 10.0, 30.0):
             p, e = (pe, 0.0) if pe >= 0 else (0.0, -pe)
             q, qa = C.c_double(q0), C.c_double()
-            assert L.oracle_kirchner_step(c1, c2, c3, 1e-7, 1e-8, 0, HOUR, C.byref(q), C.byref(qa), p, e) == 0
+            assert L.oracle_kirchner_step(c1, c2, c3, 1e-7, 1e-8, 0, dt_us, C.byref(q), C.byref(qa), p, e) == 0
 
             def f(t, x):
                 g = np.exp(c1 + c2 * x[0] + c3 * x[0] ** 2)
                 return [g * ((p - e) * np.exp(-x[0]) - 1.0) if g >= 1e-30 else 0.0]
 
-            s = scipy_integrate.solve_ivp(f, (0.0, 1.0), [np.log(max(q0, 1e-5))], method="DOP853", rtol=1e-13,
+            s = scipy_integrate.solve_ivp(f, (0.0, dt_us / HOUR), [np.log(max(q0, 1e-5))], method="DOP853", rtol=1e-13,
                                           atol=1e-14)
             qe = float(np.exp(s.y[0, -1]))
             worst = max(worst, abs(q.value - qe) / qe)
+    print(f"dt {dt_s} s: worst relative distance {worst:.3g}")
     assert worst <= 5e-7, worst
